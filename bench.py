@@ -11,6 +11,11 @@ ONE JSON line.
 Metric: Gcell-updates/s = H*W*generations / time (sub-iterations not counted), the reference's definition
 (scripts/benchmark-common.jl:97-98,122).
 
+A plain run sets up, warms up, times `--steps` steps and prints the line with what the headline needs.  Everything
+else this file measures or checks -- `verified`, `roofline`, `legs`, `cpu_baseline` below -- runs with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed as .npy files (see dump_outputs()); the input is
+the same deterministic grid in every run, so two builds can be compared output for output.
+
 N > 1 is BASELINE's series (metric "16384^2, 1/2/4/8 GPU"): STRONG scaling -- the
 same 16384^2 grid cut into N row strips, ghost rows exchanged with the two neighbours over RCCL by the native
 strip driver of libststhip.so (no collective on the data path).  `--config5` runs the 65536^2 grid of configs[4]
@@ -18,7 +23,7 @@ instead (also strong: 65536/N rows per rank; its 1-GPU point fits one MI355X).  
 rows per rank instead (weak scaling).  If the RCCL communicator cannot be created the run FAILS (exit code 3)
 unless `--allow-fallback` asks for the torch.distributed driver instead.
 
-What the JSON line carries besides the contract's fields:
+What the JSON line carries besides the contract's fields with `--full`:
   roofline      the dominant kernel measured live with HIP events on the launch stream (full-grid launches of
                 the deepest compiled blocking depth).  `achieved` / `frac` are SURVEY 8d's ALGORITHMIC bytes
                 (8 B per cell-update x generations per launch) over the launch time -- with temporal blocking
@@ -88,9 +93,15 @@ def parse_args():
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: if the native RCCL communicator cannot be created, run the torch.distributed "
                          "driver (stencilstream_amd/dist.py) instead of failing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the template_api / hotspot / fdtd legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the last timed step, time the roofline's full-grid launches and run the kernel "
+                         "legs and the CPU baseline (a plain run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed into DIR as .npy files (float32 cells, float64 "
+                         "flat indices)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the verification")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the template_api / hotspot / fdtd legs")
     ap.add_argument("--profile-legs", action="store_true",
                     help="run every kernel leg three times and nothing else (the program tools/profile_bench_r04.sh "
                          "profiles); prints the sequence of legs instead of the bench line")
@@ -102,7 +113,10 @@ def parse_args():
                     help="one full-grid launch per pass (no row strips on side streams)")
     ap.add_argument("--cpu-size", type=int, default=8192)
     ap.add_argument("--cpu-generations", type=int, default=192)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -597,6 +611,39 @@ def profile_legs(torch, capi, device, stream, gens):
     print(json.dumps({"profile_legs": sequence}), flush=True)
 
 
+DUMP_SAMPLE_CELLS = 1 << 21  # a grid of more cells is written as this fixed, seeded sample (8 + 16 MB)
+DUMP_SAMPLE_SEED = 0x5EED
+DUMP_WINDOW = 512  # ... and a full-resolution window across the NW corner of the centred square
+
+
+def dump_outputs(directory, torch, rows, row0, total_rows, W, prefix="jacobi"):
+    """`--dump-outputs`: what the last timed step left, `rows` (= rows row0.. of the total_rows x W grid, on the
+    device), as .npy files in `directory`.  A grid of at most DUMP_SAMPLE_CELLS cells is written whole
+    (<prefix>_grid.npy); a larger one as the cells at a fixed, seeded set of flat indices into the WHOLE grid
+    (<prefix>_sample.npy float32, <prefix>_sample_index.npy float64, exact), of which a rank keeps those in its own
+    rows, and, when the rank holds it, a DUMP_WINDOW^2 window across the NW corner of the centred square, where the
+    generations change the cells (<prefix>_window.npy)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    n_rows = rows.shape[0]
+    cells = total_rows * W
+    if cells <= DUMP_SAMPLE_CELLS:
+        np.save(os.path.join(directory, f"{prefix}_grid.npy"), rows.cpu().numpy().astype(np.float32))
+        return
+    index = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, cells, DUMP_SAMPLE_CELLS, dtype=np.int64))
+    index = index[(index >= row0 * W) & (index < (row0 + n_rows) * W)]
+    local = torch.from_numpy(index - row0 * W).to(rows.device)
+    values = rows.reshape(-1)[local].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(directory, f"{prefix}_sample.npy"), values)
+    np.save(os.path.join(directory, f"{prefix}_sample_index.npy"), index.astype(np.float64))
+    w = min(DUMP_WINDOW, total_rows, W)
+    r0, c0 = max(0, min(total_rows // 4 - w // 2, total_rows - w)), max(0, min(W // 4 - w // 2, W - w))
+    if row0 <= r0 and r0 + w <= row0 + n_rows:
+        window = rows[r0 - row0:r0 - row0 + w, c0:c0 + w].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(directory, f"{prefix}_window.npy"), window)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -774,6 +821,14 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        # before anything else runs on the grids: the verification and the roofline below overwrite them
+        if world == 1 and not args.strip_domain:
+            dump_outputs(args.dump_outputs, torch, dst, 0, H, W)
+        else:
+            dump_outputs(args.dump_outputs, torch, owned_rows(), a, total_rows, W,
+                         prefix="jacobi" if world == 1 else f"jacobi_rank{rank}")
+
     strips_verified, strips_report = None, None
     if world > 1 or args.strip_domain:
         import torch.distributed as dist
@@ -783,7 +838,7 @@ def main():
             t = torch.tensor([elapsed], device="cpu" if cpu_side else device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             # The strips' state has advanced through warm-up and timed steps, so the check runs ONE more step from
             # the initial grid with the very same driver (outside the timed region) and compares every rank's rows,
             # bit for bit, with the same generations of the WHOLE grid computed on this rank's own GPU by the
@@ -857,6 +912,7 @@ def main():
         if world == 1 and not args.strip_domain:
             launches_per_step = int(last["info"].n_launches)
             out["launches_per_step"] = launches_per_step
+        if world == 1 and not args.strip_domain and args.full:
             if not args.no_verify:
                 ok, report = verify_timed(torch, capi, p, halo, dom, src, dst, gens, stream, total_rows, W)
                 out["verified"] = bool(ok)

@@ -50,7 +50,7 @@ def test_bench_two_ranks_on_one_gpu_run_plainly():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--debug-host-exchange",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--debug-host-exchange",
                           "--steps", "2", "--warmup", "1", "--size", "4096", "--generations", "100",
                           "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -71,7 +71,7 @@ def test_bench_two_ranks_exchange_every_four_launches():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--debug-host-exchange",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--debug-host-exchange",
                           "--steps", "1", "--warmup", "1", "--size", "4096", "--generations", "100",
                           "--exchange-every", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
                          env=env, cwd=ROOT)

@@ -10,7 +10,7 @@ export STSTHIP_BENCH_MINIMAL=1
 for round in 1 2 3; do
     for which in "$A" "$B"; do
         cp "$which" stencilstream_amd/libststhip.so
-        python bench.py "$@" 2>/dev/null | python -c "
+        python bench.py --full "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$which', d['value'], d['roofline'].get('kernel_ms'))"
     done

@@ -3,4 +3,4 @@
 # rows travel through host memory over gloo.  The number it prints is NOT a multi-GPU result.
 cd "$(dirname "$0")/.."
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 2 --steps 2 --warmup 1 --rows-per-gpu ${ROWS:-8192} --debug-host-exchange "$@"
+    bench.py --full --gpus 2 --steps 2 --warmup 1 --rows-per-gpu ${ROWS:-8192} --debug-host-exchange "$@"

@@ -2,7 +2,7 @@
 # Hardware queues (GPU_MAX_HW_QUEUES, read by the HIP runtime at start) against the pass driver's strips with moving boundaries
 # (no band streams any more) and the strip driver's sub-strips: does a third stream pay when it has a queue of its own?
 for q in 4 8; do for v in 2 3; do
-  GPU_MAX_HW_QUEUES=$q STSTHIP_VIRTUAL_STRIPS=$v python bench.py --gpus 1 --steps 8 --warmup 2 --no-cpu-baseline --no-legs 2>/dev/null > /tmp/hwq.json
+  GPU_MAX_HW_QUEUES=$q STSTHIP_VIRTUAL_STRIPS=$v python bench.py --full --gpus 1 --steps 8 --warmup 2 --no-cpu-baseline --no-legs 2>/dev/null > /tmp/hwq.json
   python3 - $q $v <<'PY'
 import json, sys
 d = json.loads(open("/tmp/hwq.json").read().strip().splitlines()[-1])

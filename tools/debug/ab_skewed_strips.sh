@@ -1,7 +1,7 @@
 #!/bin/bash
 # Two strips with a moving boundary (STSTHIP_SKEWED_STRIPS=1) against two strips with boundary bands, every bench leg.
 for m in 0 1 0 1; do
-  STSTHIP_SKEWED_STRIPS=$m python bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null > /tmp/ab_skew_$m.json
+  STSTHIP_SKEWED_STRIPS=$m python bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null > /tmp/ab_skew_$m.json
   python3 - $m <<'PY'
 import json, sys
 m = sys.argv[1]

@@ -5,7 +5,7 @@ OUT="$REPO/gpurun_out/sq_strip"; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 C="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES"
 timeout -k 10 280 rocprofv3 --pmc $C --output-format csv -d "$OUT/strip" -- python3 "$REPO/tools/bench_strip.py" --rows 2048 --exchange-every 4 --reps 1 > "$OUT/strip.log" 2>&1 || echo "strip pass failed"
-STSTHIP_BENCH_MINIMAL=1 timeout -k 10 280 rocprofv3 --pmc $C --output-format csv -d "$OUT/full" -- python3 "$REPO/bench.py" --gpus 1 --steps 2 --warmup 1 --no-verify > "$OUT/full.log" 2>&1 || echo "full pass failed"
+STSTHIP_BENCH_MINIMAL=1 timeout -k 10 280 rocprofv3 --pmc $C --output-format csv -d "$OUT/full" -- python3 "$REPO/bench.py" --full --gpus 1 --steps 2 --warmup 1 --no-verify > "$OUT/full.log" 2>&1 || echo "full pass failed"
 python3 - "$OUT" <<'PY'
 import collections, csv, glob, json, sys
 out = sys.argv[1]

@@ -5,7 +5,7 @@ out=gpurun_out/sweep_fdtd.txt
 : > $out
 run() {
   echo "## $*" >> $out
-  env "$@" python3 bench.py --no-cpu-baseline --no-verify --steps 2 --warmup 1 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); l=d['legs']; print(round(l['fdtd_max_grid']['value'],1), round(l['hotspot_8192']['value'],1), round(l['general_coefficients']['value'],1))" >> $out
+  env "$@" python3 bench.py --full --no-cpu-baseline --no-verify --steps 2 --warmup 1 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); l=d['legs']; print(round(l['fdtd_max_grid']['value'],1), round(l['hotspot_8192']['value'],1), round(l['general_coefficients']['value'],1))" >> $out
 }
 run A=0
 run STSTHIP_VIRTUAL_STRIPS=1

@@ -2,7 +2,7 @@
 # Launcher knobs on the bench headline now that the strips have no boundary bands: tail weight of the chunk rule, taper.
 run() { # label, env...
   label=$1; shift
-  env "$@" python bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-legs 2>/dev/null > /tmp/knob.json
+  env "$@" python bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-legs 2>/dev/null > /tmp/knob.json
   python3 - "$label" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/knob.json").read().strip().splitlines()[-1])

@@ -16,7 +16,7 @@ tail -n 1 "$OUT/stats.log" | cut -c 1-400
 export STSTHIP_BENCH_MINIMAL=1
 for PASS in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES"; do
     set -- $PASS; NAME=$1; shift
-    rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$NAME" -- python3 "$REPO/bench.py" --gpus 1 --steps 2 --warmup 1 --no-verify > "$OUT/$NAME.log" 2> "$OUT/$NAME.err"
+    rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$NAME" -- python3 "$REPO/bench.py" --full --gpus 1 --steps 2 --warmup 1 --no-verify > "$OUT/$NAME.log" 2> "$OUT/$NAME.err"
     echo "pmc pass $NAME done"
 done
 python3 "$REPO/tools/summarize_bench_profile.py" "$TAG"
