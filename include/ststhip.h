@@ -340,7 +340,9 @@ typedef struct {
      * same five-point Jacobi source is nine operations per cell compiled with -ffp-contract=off and five with fused
      * multiply-adds: the first is fastest at 8 generations per launch, the second at 16), and a small grid pays more
      * for deep halos than a large one.  `alt_generations` names a second depth `sweep` accepts (a repeated halving of
-     * max_generations) and is the depth of every launch nobody has measured; on the first call for a grid shape that is
+     * max_generations: any other value is refused with STSTHIP_ERR_INVALID) and is the depth of every launch nobody has
+     * measured.  Where alt_generations does not divide max_generations (18 -> 9 -> 4), or both are odd (27 and 3),
+     * nothing is measured: every launch runs at alt_generations.  Otherwise, on the first call for a grid shape that is
      * long enough (>= 6 launches of max_generations) the pass driver times two launches of max_generations against the
      * same generations at alt_generations -- these are the call's own first passes, no work is repeated --, keeps the
      * faster for the rest of the call and, per (tune_key, height, width), for the process
@@ -359,7 +361,8 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
  * it.  A host that uploads in ROW BLOCKS (in order, first rows first) names them here for the calling thread's NEXT
  * ststhip_run_passes / ststhip_app_run call: rows [blocks[i-1].row_end, blocks[i].row_end) of every source plane are in
  * HBM once event blocks[i].ready has completed (the last row_end >= the grid's height; the call consumes the list
- * whatever it returns).  The driver then starts on what has arrived: it runs its first passes as row tiles skewed in
+ * whatever it returns, also when it refuses its arguments before any work: a later call never sees it).  The driver
+ * then starts on what has arrived: it runs its first passes as row tiles skewed in
  * time -- pass p of the rows above block boundary b reaches g*(p+1) rows less far down than the boundary, g = ghost
  * rows of one launch, so that every tile depends only on tiles of rows that arrived earlier --, as many passes deep
  * as it takes to keep the chip busy between two arrivals (measured per call: the first tile column is timed against

@@ -86,6 +86,32 @@ class SourceBlock(C.Structure):
     _fields_ = [("row_end", C.c_uint64), ("ready", C.c_void_p)]
 
 
+SWEEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(Domain), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                       C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p)
+"""ststhip_sweep_fn: (ctx, dom, src, dst, out_row_begin, out_row_end, iteration, n_generations, stream) -> status"""
+
+FILL_TDV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+"""ststhip_sweep_desc::fill_tdv: (ctx, iteration_offset, n_iterations, values)"""
+
+
+class SweepDesc(C.Structure):
+    """ststhip_sweep_desc"""
+
+    _fields_ = [
+        ("n_planes", C.c_uint32),
+        ("max_generations", C.c_uint32),
+        ("halo_depth_per_generation", C.c_uint32),
+        ("strip_width", C.c_uint32),
+        ("plane_elem_size", C.c_uint64 * 16),
+        ("tdv_size", C.c_uint64),
+        ("fill_tdv", FILL_TDV_FN),
+        ("tdv_device_table", C.c_void_p),
+        ("alt_generations", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("tune_key", C.c_uint64),
+    ]
+
+
 class JacobiParams(C.Structure):
     _fields_ = [("coef", C.c_float * 9)]
 
@@ -209,6 +235,7 @@ def load():
         "ststhip_kernel_scratch_bytes": [vp, C.POINTER(sz)],
         "ststhip_launch_concurrency": [],
         "ststhip_target_holds_constants": [],
+        "ststhip_current_tdv_table": [pp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)],
         "ststhip_set_launch_concurrency": [C.c_int],
         "ststhip_launch_row_hole": [C.POINTER(u64), C.POINTER(u64)],
         "ststhip_set_launch_row_hole": [u64, u64],
@@ -224,8 +251,8 @@ def load():
         "ststhip_app_sweep": [C.c_char_p, vp, vp, C.POINTER(Domain), pp, pp, u64, u64, u64, u32, vp],
         "ststhip_app_run": [C.c_char_p, vp, vp, C.POINTER(Domain), pp, pp, u64, u64, C.c_int, C.c_int,
                             vp, C.POINTER(RunInfo)],
-        "ststhip_run_passes": [vp, vp, vp, C.POINTER(Domain), pp, pp, u64, u64, C.c_int, C.c_int, vp,
-                               C.POINTER(RunInfo)],
+        "ststhip_run_passes": [SWEEP_FN, vp, C.POINTER(SweepDesc), C.POINTER(Domain), pp, pp, u64, u64, C.c_int,
+                               C.c_int, vp, C.POINTER(RunInfo)],
         "ststhip_set_source_arrival": [C.POINTER(SourceBlock), u32],
         "ststhip_suggest_upload_blocks": [u64, u64, C.POINTER(u32)],
         "ststhip_upload_streams": [pp, pp],
@@ -401,6 +428,93 @@ def app_run(app, tf_params, halo_bytes, dom, src_ptrs, dst_ptrs, iteration_offse
         f"ststhip_app_run({app})",
     )
     return info
+
+
+def sweep_desc_of(app, alt_generations=0, tune_key=0):
+    """The description ststhip_app_run hands to the pass driver for a precompiled transition function, with the
+    second depth and the key of its measurements as given (0 / 0: one depth, nothing measured)."""
+    info = app_info(app)
+    desc = SweepDesc()
+    desc.n_planes = info.n_planes
+    desc.max_generations = info.max_generations
+    desc.halo_depth_per_generation = info.halo_depth_per_generation
+    desc.strip_width = info.strip_width
+    for p in range(info.n_planes):
+        desc.plane_elem_size[p] = info.plane_elem_size[p]
+    desc.alt_generations = int(alt_generations)
+    desc.tune_key = int(tune_key)
+    return desc
+
+
+def run_passes(sweep, desc, dom, src_ptrs, dst_ptrs, iteration_offset, n_iterations, blocking=True, profiling=False,
+               stream=0):
+    """ststhip_run_passes with a Python launch callback: `sweep(dom, src, dst, out_row_begin, out_row_end, iteration,
+    n_generations, stream)` with `src` / `dst` tuples of the n_planes device pointers and `stream` the handle to launch
+    on.  It is called on the calling thread, once per launch, in the order in which the driver enqueues; the thread's
+    launch state (launch_row_hole, target_holds_constants, launch_concurrency, current_tdv_table) is the launch's.  An
+    exception it raises ends the call with an error and is raised again here."""
+    _sync_options()
+    n_planes = int(desc.n_planes)
+    raised = []
+
+    def trampoline(_ctx, dom_p, src_p, dst_p, out_begin, out_end, iteration, n_generations, launch_stream):
+        try:
+            sweep(dom_p.contents, tuple(src_p[i] or 0 for i in range(n_planes)),
+                  tuple(dst_p[i] or 0 for i in range(n_planes)), int(out_begin), int(out_end), int(iteration),
+                  int(n_generations), launch_stream or 0)
+            return 0
+        except StsthipError as e:
+            raised.append(e)
+            return e.status
+        except BaseException as e:  # noqa: BLE001 -- reported through the C ABI's status, raised again below
+            raised.append(e)
+            load().ststhip_set_last_error(str(e).encode())
+            return 2
+
+    callback = SWEEP_FN(trampoline)
+    info = RunInfo()
+    status = load().ststhip_run_passes(callback, None, C.byref(desc), C.byref(dom), _ptr_array(src_ptrs),
+                                       _ptr_array(dst_ptrs), int(iteration_offset), int(n_iterations),
+                                       int(bool(blocking)), int(bool(profiling)), C.c_void_p(int(stream)),
+                                       C.byref(info))
+    if raised:
+        raise raised[0]
+    check(status, "ststhip_run_passes")
+    return info
+
+
+def tuned_depth(tune_key, height, width):
+    """Depth the pass driver has measured to be the faster one for (tune_key, height, width); 0: not measured."""
+    depth = C.c_uint32()
+    check(load().ststhip_tuned_depth(int(tune_key), int(height), int(width), C.byref(depth)), "ststhip_tuned_depth")
+    return int(depth.value)
+
+
+def launch_row_hole():
+    """(begin, end) of the rows the calling thread's launches leave out (ststhip_launch_row_hole); empty when
+    begin >= end."""
+    a, b = C.c_uint64(), C.c_uint64()
+    check(load().ststhip_launch_row_hole(C.byref(a), C.byref(b)), "ststhip_launch_row_hole")
+    return int(a.value), int(b.value)
+
+
+def target_holds_constants():
+    """1 inside a pass-driver launch whose target already holds the fields that never change."""
+    return int(load().ststhip_target_holds_constants())
+
+
+def launch_concurrency():
+    """Row-range sweeps the calling thread's driver keeps in flight side by side."""
+    return int(load().ststhip_launch_concurrency())
+
+
+def current_tdv_table():
+    """(base, first_iteration, n_values, value_size) of the device table of time-dependent values of the pass-driver
+    call the calling thread is in (base 0: none)."""
+    base, first, count, size = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(load().ststhip_current_tdv_table(C.byref(base), C.byref(first), C.byref(count), C.byref(size)),
+          "ststhip_current_tdv_table")
+    return base.value or 0, int(first.value), int(count.value), int(size.value)
 
 
 def suggest_upload_blocks(rows, row_bytes):

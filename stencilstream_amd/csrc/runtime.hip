@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -1307,6 +1308,14 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
         return fail(STSTHIP_ERR_INVALID, "bad sweep description");
     if (dom->row_origin != 0 || dom->local_rows != dom->global_height)
         return fail(STSTHIP_ERR_INVALID, "the pass driver works on whole grids (row_origin 0)");
+    // the second depth is one the sweep is compiled for: max_generations or one of its repeated halvings
+    if (desc->alt_generations != 0) {
+        std::uint32_t t = desc->max_generations;
+        while (t > desc->alt_generations)
+            t /= 2;
+        if (t != desc->alt_generations)
+            return fail(STSTHIP_ERR_INVALID, "alt_generations must be a repeated halving of max_generations");
+    }
     if (int rc = ststhip_init(-1))
         return rc;
     hipStream_t s = resolve(stream);
@@ -1318,8 +1327,13 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
     // The depth plan.  With a second candidate depth (desc->alt_generations) the first call for a grid shape times its
     // own first passes at both depths and keeps the faster (ststhip.h, ststhip_sweep_desc); later calls look it up.
     const std::uint32_t deep = desc->max_generations, alt = desc->alt_generations;
-    const bool tunable = desc->tune_key != 0 && alt >= 2 && alt < deep && deep % alt == 0 && !profiling &&
-                         opt().tune_depth == 1 && opt().max_generations <= 0;
+    // (`alt` must divide `deep`: the probes time two launches of `deep` against the SAME generations at `alt`; a
+    // repeated halving need not: 18 -> 9 -> 4, 14 -> 7 -> 3.  And one of the two must be even: the two plans of a
+    // probing call are brought to the same parity by halving one pass, see below; 27 -> 13 -> 6 -> 3 has none to
+    // halve.  A family that fails either is not measured, it runs at `alt`)
+    const bool tunable = desc->tune_key != 0 && alt >= 2 && alt < deep && deep % alt == 0 &&
+                         (alt % 2 == 0 || deep % 2 == 0) && !profiling && opt().tune_depth == 1 &&
+                         opt().max_generations <= 0;
     // (a family with a second depth runs it wherever nothing has been measured: that is the depth its rule trusts)
     std::uint32_t depth_cap = (alt >= 1 && alt < deep) ? alt : 0;
     bool probing = false;
@@ -1337,12 +1351,15 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
     std::vector<std::uint32_t> depths;
     // a probing call: [deep (untimed: clocks and caches settle)] [deep, deep] [alt x 2*deep/alt] then the rest at the
     // winner's depth, planned once the probes have been timed.  The ping-pong parity of the targets must be fixed
-    // before that: it is that of the plan that continues at `deep`; if the other plan wins with the other parity, one
-    // of its passes is split into two of half its depth.
+    // before that: it is that of the plan that continues at `deep`; if the other plan has the other parity, one of its
+    // passes is split into two of half its depth -- or, where `alt` is odd (every compiled depth up to it is odd then:
+    // the number of passes at `alt` has the parity of the generations left, whatever is split; half of 3 is 1, and
+    // 1 + 1 loses a generation), one pass of the plan that continues at `deep`.
     const std::size_t probe_passes = probing ? 3 + 2 * (deep / alt) : 0;
     std::vector<std::uint32_t> rest_alt;
-    // (a lambda: planned again for what is left once the passes behind an arriving source have run)
-    auto plan = [&](std::uint64_t n) {
+    // (a lambda: planned again for what is left once the passes behind an arriving source have run; false: the plan
+    // does not advance `n` generations, whichever depth wins -- a wrong grid must not leave this call)
+    auto plan = [&](std::uint64_t n) -> bool {
         depths.clear();
         rest_alt.clear();
         if (probing) {
@@ -1351,23 +1368,30 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
             for (std::uint32_t i = 0; i < 2 * (deep / alt); i++)
                 depths.push_back(alt);
             const std::uint64_t left = n - 5ull * deep;
-            const std::vector<std::uint32_t> rest_deep = plan_depths(left, deep);
+            std::vector<std::uint32_t> rest_deep = plan_depths(left, deep);
             rest_alt = plan_depths(left, deep, alt);
             if ((rest_alt.size() + rest_deep.size()) % 2 != 0) {
-                // split the first pass of depth `alt` (there is one: left >= deep) into two of alt / 2
-                for (std::size_t i = 0; i < rest_alt.size(); i++)
-                    if (rest_alt[i] == alt) {
-                        rest_alt[i] = alt / 2;
-                        rest_alt.insert(rest_alt.begin() + i, alt / 2);
+                // split the first pass of depth `alt` (there is one: left >= deep) into two of alt / 2; an odd `alt`:
+                // the first pass of depth `deep` (even: see `tunable`) of the other plan into two of deep / 2
+                std::vector<std::uint32_t> &split_in = alt % 2 == 0 ? rest_alt : rest_deep;
+                const std::uint32_t whole = alt % 2 == 0 ? alt : deep;
+                for (std::size_t i = 0; i < split_in.size(); i++)
+                    if (split_in[i] == whole) {
+                        split_in[i] = whole / 2;
+                        split_in.insert(split_in.begin() + i, whole / 2);
                         break;
                     }
             }
             depths.insert(depths.end(), rest_deep.begin(), rest_deep.end()); // replaced by rest_alt if alt wins
+            if (std::accumulate(rest_alt.begin(), rest_alt.end(), std::uint64_t(0)) != left)
+                return false;
         } else {
             depths = plan_depths(n, deep, depth_cap);
         }
+        return std::accumulate(depths.begin(), depths.end(), std::uint64_t(0)) == n;
     };
-    plan(n_iterations);
+    if (!plan(n_iterations))
+        return fail(STSTHIP_ERR_INVALID, "internal: the depth plan does not sum to the generations asked for");
     // The passes the whole call takes; which of `dst` and the scratch planes a pass writes follows from its index and
     // this number alone (the last one writes `dst`).
     const std::size_t total_passes = depths.size();
@@ -1598,9 +1622,11 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
                 if (frontier[p] != H)
                     rc = fail(STSTHIP_ERR_INVALID, "internal: a streamed pass is incomplete");
             if (rc == STSTHIP_OK && streamed > 0) {
-                plan(n_iterations - streamed * tile_depth);
+                if (!plan(n_iterations - streamed * tile_depth))
+                    rc = fail(STSTHIP_ERR_INVALID,
+                              "internal: the depth plan does not sum to the generations asked for");
                 // (a probing call's plans differ in length by whole pairs of passes)
-                if ((streamed + depths.size()) % 2 != total_passes % 2)
+                else if ((streamed + depths.size()) % 2 != total_passes % 2)
                     rc = fail(STSTHIP_ERR_INVALID, "internal: the plan behind the streamed passes has another parity");
                 strips = suggest_row_strips(H, dom->global_width, desc->strip_width, g_max, depths.size());
             }
@@ -2017,6 +2043,11 @@ int ststhip_app_run(const char *app, const void *tf_params, const void *halo_cel
                     const ststhip_domain *dom, const void *const *src, void *const *dst,
                     uint64_t iteration_offset, uint64_t n_iterations, int blocking, int profiling,
                     ststhip_stream stream, ststhip_run_info *info) {
+    // the list of a source that is still arriving is for this call, whatever it returns: the pass driver takes it
+    // first thing, and a return before that must not leave it to the thread's next call
+    struct ConsumeArrival {
+        ~ConsumeArrival() { source_arrival().clear(); }
+    } consume_arrival;
     const AppEntry *e = find_app(app);
     if (!e)
         return fail(STSTHIP_ERR_UNKNOWN_APP, "unknown transition function");
