@@ -15,13 +15,20 @@
 //
 // What differs by design: instead of one kernel per (iteration, sub-iteration), one kernel
 // advances up to SweepTuning<F>::max_generations generations (hip/internal/Sweep.hpp).
+//
+// Beyond the reference's interface: get_sweep_form() -- a function that declares itself a linear five-point cross
+// (LinearForm.hpp) and is found to be one is swept by the product-carrying form of the five-point Jacobi where its
+// coefficients and the halo allow it: the same cells bit for bit, five instead of nine operations per cell.
 #pragma once
 #include "../Concepts.hpp"
 #include "../tdv/SinglePassStrategies.hpp"
 #include "Grid.hpp"
+#include "LinearForm.hpp"
 #include "internal/Sweep.hpp"
 
 #include <chrono>
+#include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -76,6 +83,15 @@ class StencilUpdate {
             return false;
     }();
     using Planes = internal::PlaneSet<Cell, on_planes>;
+    // May this instantiation be routed to the uniform five-point form at all?  (What else has to hold is a matter of
+    // the parameters of a call: choose_form.)  Only then is the probe instantiated.
+    static constexpr bool linear_candidate = [] {
+        if constexpr (internal::DeclaresLinearCross5<F>)
+            return std::is_same_v<Cell, float> && F::stencil_radius == 1 && F::n_subiterations == 1 && !has_tdv &&
+                   !split_cell_structure;
+        else
+            return false;
+    }();
 
   public:
     using GridImpl = Grid<Cell>;
@@ -97,9 +113,13 @@ class StencilUpdate {
         // inside the first call, where it used to hide behind the grid's upload and would now sit in front of the
         // passes that follow the upload block by block (simulate()).  A host without a usable GPU learns so from
         // operator(), as before.
+        // ... and where the function declares a linear form, the declaration is checked here, once (LinearForm.hpp).
         try {
             internal::ensure_runtime(params.device.hip_index());
             (void)spill_free_depth();
+            if constexpr (linear_candidate)
+                if (internal::form_knobs().route)
+                    linear_form.take(this->params.transition_function, this->params.halo_value);
         } catch (...) {
         }
     }
@@ -107,10 +127,13 @@ class StencilUpdate {
     Params &get_params() { return params; }
     std::size_t get_n_processed_cells() const { return n_processed_cells; }
     double get_walltime() const { return walltime; }
+    // The form of the sweep the most recent call ran (general before any call).
+    SweepForm get_sweep_form() const { return sweep_form; }
 
     // For drivers other than operator() (hip/StripUpdate.hpp: one strip of a grid cut over several GPUs): the launch
     // callback of this instantiation -- its context is a pointer to this object, which must stay where it is -- and
-    // the description ststhip_run_passes / ststhip_strip_create_custom plan their passes with.
+    // the description ststhip_run_passes / ststhip_strip_create_custom plan their passes with.  Both describe F's
+    // general sweep, whatever form operator() takes: those drivers' ghost cells are F's cells, not products.
     static ststhip_sweep_fn launch_entry() { return &sweep_trampoline; }
     static ststhip_sweep_desc sweep_description() {
         ststhip_sweep_desc desc = {};
@@ -207,6 +230,85 @@ class StencilUpdate {
         }
     }
 
+    // The same for a call that runs the uniform five-point form.  Its kernels are the ones libststhip.so holds
+    // precompiled for ststhip_app_run("jacobi5general") (forms/Jacobi5Uniform.hpp, built without contraction): this
+    // translation unit compiles none of them, whatever its own flags are.  Which of the four a launch needs depends on
+    // whether it holds the first and / or the last generation of the call (the rule of the library's own trampoline).
+    static int uniform_trampoline(void *ctx, const ststhip_domain *dom, const void *const *src, void *const *dst,
+                                  std::uint64_t out_begin, std::uint64_t out_end, std::uint64_t iteration,
+                                  std::uint32_t depth, ststhip_stream stream)
+        requires(linear_candidate)
+    {
+        StencilUpdate const *self = static_cast<StencilUpdate const *>(ctx);
+        const bool first = iteration == self->params.iteration_offset;
+        const bool last = iteration + depth - 1 == self->params.iteration_offset + self->params.n_iterations - 1;
+        const char *form = first ? (last ? "jacobi5uniform_only" : "jacobi5uniform_first")
+                                 : (last ? "jacobi5uniform_last" : "jacobi5uniform");
+        const struct {
+            float c;
+        } block = {self->linear_form.verdict.coef[0]};
+        return ststhip_app_sweep(form, &block, &self->params.halo_value, dom, src, dst, out_begin, out_end, iteration,
+                                 depth, stream);
+    }
+    // the uniform form's description for the pass driver, from the library's registry; false: this library has no such
+    // kernels
+    static bool uniform_description(ststhip_sweep_desc &desc)
+        requires(linear_candidate)
+    {
+        ststhip_app_info info;
+        for (const char *form : {"jacobi5uniform", "jacobi5uniform_first", "jacobi5uniform_last", "jacobi5uniform_only"})
+            if (ststhip_app_find(form, &info) != STSTHIP_OK || info.n_planes != 1 || info.cell_size != sizeof(float))
+                return false;
+        desc = {};
+        desc.n_planes = info.n_planes;
+        desc.max_generations = info.max_generations;
+        desc.halo_depth_per_generation = info.halo_depth_per_generation;
+        desc.strip_width = info.strip_width;
+        desc.plane_elem_size[0] = info.plane_elem_size[0];
+        return true;
+    }
+
+    // The form of this call, and for the general one the first condition that failed.
+    SweepForm choose_form(const char *&why_general) {
+        why_general = nullptr;
+        if constexpr (!std::is_same_v<Cell, float>)
+            why_general = "the cell is not a float";
+        else if constexpr (F::stencil_radius != 1)
+            why_general = "the stencil radius is not 1";
+        else if constexpr (F::n_subiterations != 1)
+            why_general = "the function has sub-iterations";
+        else if constexpr (has_tdv)
+            why_general = "the function has a time-dependent value";
+        else if constexpr (split_cell_structure)
+            why_general = "split_cell_structure";
+        else if constexpr (!internal::DeclaresLinearCross5<F>)
+            why_general = "the function declares no LinearCross5";
+        else {
+            if (!internal::form_knobs().route) {
+                why_general = "STSTHIP_LINEAR_FORM=0";
+                return SweepForm::general;
+            }
+            // probed again only when get_params() was used to change the function or the halo
+            if (!linear_form.holds(params.transition_function, params.halo_value))
+                linear_form.take(params.transition_function, params.halo_value);
+            std::uint32_t halo_bits;
+            std::memcpy(&halo_bits, &params.halo_value, sizeof halo_bits);
+            if (!linear_form.verdict.verified)
+                why_general = linear_form.verdict.reason;
+            else if (!internal::uniform_positive(linear_form.verdict.coef))
+                why_general = "the five coefficients are not one positive finite number";
+            else if (halo_bits != 0u)
+                why_general = "halo_value is not +0";
+            else if (params.n_iterations == 0)
+                why_general = "no generations to run";
+            else if (ststhip_sweep_desc desc; !uniform_description(desc))
+                why_general = "libststhip.so holds no jacobi5uniform kernels";
+            else
+                return SweepForm::jacobi5_uniform;
+        }
+        return SweepForm::general;
+    }
+
     // SweepTuning's generic rule sizes the pipeline by the cell alone.  A transition function with a lot of state of
     // its own (FDTD's RenderResolver: sixteen ring bounds and material sets compared per cell) can need far more
     // registers; the compiler then builds the deep kernels with spills to scratch, and they run several times slower
@@ -234,6 +336,26 @@ class StencilUpdate {
     // All passes of one call, from `source` planes into `target` planes.
     void run_passes(ststhip_domain const &dom, Planes const &source, Planes const &target,
                     ststhip_stream stream, std::vector<ststhip_source_block> const &arriving = {}) {
+        const char *why_general = nullptr;
+        sweep_form = choose_form(why_general);
+        internal::trace_form(sweep_form, why_general);
+        if constexpr (linear_candidate) {
+            // the uniform form behind the same pass driver: streamed upload, moving strips, swap planes as ever
+            if (sweep_form == SweepForm::jacobi5_uniform) {
+                ststhip_sweep_desc desc;
+                (void)uniform_description(desc);
+                ststhip_run_info info = {};
+                internal::check(ststhip_set_source_arrival(arriving.data(), std::uint32_t(arriving.size())),
+                                "ststhip_set_source_arrival");
+                internal::check(ststhip_run_passes(&uniform_trampoline, this, &desc, &dom,
+                                                   const_cast<const void *const *>(source.plane), target.plane,
+                                                   params.iteration_offset, params.n_iterations, 0,
+                                                   params.profiling ? 1 : 0, stream, &info),
+                                "ststhip_run_passes");
+                kernel_runtime += info.kernel_time_s;
+                return;
+            }
+        }
         ststhip_sweep_desc desc = sweep_description();
         // one device table of time-dependent values per call: filled by the host, or by the device
         void *device_values = nullptr;
@@ -289,8 +411,11 @@ class StencilUpdate {
     {
         // the reference's split path always returns a fresh grid (cuda/StencilUpdate.hpp:285,440), its AoS
         // path a handle onto the source when there is nothing to do (:206,275)
-        if (params.n_iterations == 0 && !split_cell_structure)
+        if (params.n_iterations == 0 && !split_cell_structure) {
+            sweep_form = SweepForm::general;
+            internal::trace_form(sweep_form, "no generations to run");
             return source_grid;
+        }
         ststhip_domain dom = domain_of(source_grid);
         GridImpl result = source_grid.make_similar();
         Planes from, to;
@@ -369,6 +494,10 @@ class StencilUpdate {
     std::size_t n_processed_cells;
     double walltime;
     double kernel_runtime;
+    SweepForm sweep_form = SweepForm::general;
+    // the probe's verdict for the function and halo it was taken for (nothing for functions that cannot be routed)
+    [[no_unique_address]] std::conditional_t<linear_candidate, internal::LinearFormCache<F>, internal::NoLinearFormCache>
+        linear_form;
 };
 
 } // namespace hip
