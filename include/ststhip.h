@@ -223,6 +223,51 @@ int ststhip_reduce_max_abs(const void *cells, size_t cell_size, uint64_t height,
                            uint64_t pitch, int n_fields, const ststhip_reduce_field *fields,
                            double *result, ststhip_stream stream);
 
+/* Device-side norms of up to 8 fields of a grid, or of the difference of two grids of the same layout: what "has the
+ * grid stopped changing", an L2 norm, a conservation check and "has anything become NaN" need, in one read of the
+ * cells at HBM speed (an extension, as ststhip_reduce_max_abs; additive within ABI 6).
+ *
+ * A field is the f32 / f64 of cell (row r, column c) at  base + (r * pitch + c) * stride  bytes: a member of an AoS cell
+ * (base = cells + offset of the member, stride = sizeof(Cell)) and a per-field plane (stride = size of the element;
+ * the planes of ststhip_app_run and ststhip_strip_plane) alike.  It is reduced over the rectangle
+ * [row_begin, row_end) x [col_begin, col_end), clipped to height x width; the rectangle may be empty.
+ *
+ * Every element is converted to double; the per-cell value v is the element of a (ststhip_grid_norms) or
+ * double(a) - double(b), one rounding (ststhip_grid_distance: other_base[i] is the base of field i in the second grid,
+ * same stride, pitch and rectangle).  Cells whose v is NaN or +-infinity are counted in n_nonfinite and take part in
+ * nothing else.
+ *
+ * No floating-point atomics: a lane accumulates in double, the 64 lanes of a wave and then the waves of a workgroup
+ * combine in a fixed order, every workgroup writes one partial per field and quantity and a second kernel adds the
+ * partials in index order.  The number of workgroups depends on the rectangle and the layout only, so the same call on
+ * the same data returns the same bits every time, on every device.
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID: n_fields outside 1..8, an unknown
+ * type, stride 0, a base or stride that is no multiple of the element's size, pitch < width, a null base with a
+ * non-empty rectangle).  Ordered on `stream`; synchronises it and writes `result` (host memory) before returning. */
+typedef struct {
+    const void *base;   /* the field's element of cell (0, 0)                              */
+    uint64_t stride;    /* bytes between neighbouring cells of a row                       */
+    uint64_t pitch;     /* cells between neighbouring rows (>= width)                      */
+    uint64_t height;    /* extents of the grid the rectangle is clipped to                 */
+    uint64_t width;
+    uint64_t row_begin, row_end, col_begin, col_end;
+    uint32_t type;      /* STSTHIP_F32 or STSTHIP_F64                                      */
+    uint32_t reserved;  /* 0                                                               */
+} ststhip_norm_field;
+typedef struct {
+    uint64_t n_cells;     /* cells of the clipped rectangle                                */
+    uint64_t n_nonfinite; /* of these, cells whose v is NaN or +-infinity                  */
+    double max_abs;       /* max |v| over the finite v, exact; -infinity if there is none  */
+    double sum;           /* sum of v, of |v| and of v*v over the finite v, in double      */
+    double sum_abs;
+    double sum_sq;
+} ststhip_norm_result;
+int ststhip_grid_norms(int n_fields, const ststhip_norm_field *fields, ststhip_norm_result *result,
+                       ststhip_stream stream);
+int ststhip_grid_distance(int n_fields, const ststhip_norm_field *fields, const void *const *other_base,
+                          ststhip_norm_result *result, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

@@ -159,6 +159,24 @@ class ReduceField(C.Structure):
     _fields_ = [("offset", C.c_uint32), ("type", C.c_uint32), ("row_limit", C.c_uint64), ("col_limit", C.c_uint64)]
 
 
+class NormField(C.Structure):
+    """ststhip_norm_field"""
+
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_uint64), ("pitch", C.c_uint64), ("height", C.c_uint64),
+                ("width", C.c_uint64), ("row_begin", C.c_uint64), ("row_end", C.c_uint64), ("col_begin", C.c_uint64),
+                ("col_end", C.c_uint64), ("type", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NormResult(C.Structure):
+    """ststhip_norm_result"""
+
+    _fields_ = [("n_cells", C.c_uint64), ("n_nonfinite", C.c_uint64), ("max_abs", C.c_double), ("sum", C.c_double),
+                ("sum_abs", C.c_double), ("sum_sq", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -245,6 +263,8 @@ def load():
         "ststhip_scatter_fields": [vp, sz, sz, C.c_int, C.POINTER(sz), C.POINTER(sz), pp, vp],
         "ststhip_gather_fields": [vp, sz, sz, C.c_int, C.POINTER(sz), C.POINTER(sz), pp, vp],
         "ststhip_reduce_max_abs": [vp, sz, u64, u64, u64, C.c_int, C.POINTER(ReduceField), C.POINTER(C.c_double), vp],
+        "ststhip_grid_norms": [C.c_int, C.POINTER(NormField), C.POINTER(NormResult), vp],
+        "ststhip_grid_distance": [C.c_int, C.POINTER(NormField), pp, C.POINTER(NormResult), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -597,6 +617,36 @@ def reduce_max_abs(cells_ptr, cell_size, height, width, fields, pitch=None, stre
                                         width if pitch is None else pitch, n, table, result,
                                         C.c_void_p(int(stream))), "ststhip_reduce_max_abs")
     return list(result)
+
+
+def norm_field(base, dtype, stride, height, width, pitch=None, rows=None, cols=None):
+    """A ststhip_norm_field: the `dtype` ('<f4' / '<f8') element of cell (r, c) lies at base + (r * pitch + c) * stride
+    bytes; rows / cols = (begin, end) of the rectangle, None = the whole axis."""
+    kind = {"f4": "<f4", "<f4": "<f4", "float32": "<f4", "f8": "<f8", "<f8": "<f8", "float64": "<f8"}.get(str(dtype))
+    if kind is None:
+        raise ValueError(f"grid norms reduce <f4 and <f8 elements, not {dtype}")
+    rb, re = (0, height) if rows is None else rows
+    cb, ce = (0, width) if cols is None else cols
+    return NormField(C.c_void_p(int(base)), int(stride), int(width if pitch is None else pitch), int(height),
+                     int(width), int(rb), int(re), int(cb), int(ce), 1 if kind == "<f8" else 0, 0)
+
+
+def grid_norms(fields, other=None, stream=0):
+    """ststhip_grid_norms / ststhip_grid_distance: one NormResult per NormField of `fields` (norm_field()); `other` =
+    the base addresses of the same fields in a second grid of the same layout (the values are then a - b).  Blocks
+    until the numbers are on the host; returns the ctypes array of results (bytes(result) is the C array)."""
+    n = len(fields)
+    table = (NormField * n)(*fields)
+    result = (NormResult * n)()
+    lib = load()
+    if other is None:
+        check(lib.ststhip_grid_norms(n, table, result, C.c_void_p(int(stream))), "ststhip_grid_norms")
+    else:
+        if len(other) != n:
+            raise ValueError("one base address of the second grid per field")
+        check(lib.ststhip_grid_distance(n, table, _ptr_array(other), result, C.c_void_p(int(stream))),
+              "ststhip_grid_distance")
+    return result
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -5,6 +5,7 @@ runs in libststhip.so through the C ABI.
 """
 import ctypes as C
 import time
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -71,6 +72,11 @@ def fdtd(params, split_cell_structure=True, layout=None):
     return TransitionFunction(app, params, FDTD_CELL)
 
 
+# What Grid.norms returns per field (ststhip_norm_result): over the cells of the rectangle whose value v is finite,
+# max |v| (-inf if there is none) and the sums of v, |v| and v*v in double; n_nonfinite counts the others.
+Norms = namedtuple("Norms", "n_cells n_nonfinite max_abs sum sum_abs sum_sq")
+
+
 class Grid:
     """H x W row-major AoS cells in HBM (a torch uint8 tensor of H*W*cell_size bytes)."""
 
@@ -127,6 +133,42 @@ class Grid:
 
     def domain(self):
         return capi.Domain(self.height, self.width, 0, self.height, self.width)
+
+    def norms(self, fields=None, other=None, rows=None, cols=None):
+        """Norms of the grid's float fields, computed where the cells are (ststhip_grid_norms): {field name: Norms}, the
+        key is None for a grid whose cells are plain floats.  `fields`: names of `<f4` / `<f8` members of the cell
+        (default: all of them); `other`: a grid of the same extent and cell type, the values are then this grid's minus
+        the other's, in double (ststhip_grid_distance); rows / cols = (begin, end), clipped to the grid.  Blocks until
+        the numbers are known.  A run that has converged shows in norms(other=previous)[name].max_abs; one that has
+        diverged in n_nonfinite."""
+        dt = self.cell_dtype
+        if dt.names is None:
+            if fields is not None and list(fields) != [None]:
+                raise ValueError("the cells of this grid have no named fields")
+            members = [(None, dt, 0)]
+        else:
+            floats = [n for n in dt.names if dt.fields[n][0].str in ("<f4", "<f8")]
+            names = floats if fields is None else ([fields] if isinstance(fields, str) else list(fields))
+            for n in names:
+                if n not in dt.names:
+                    raise ValueError(f"the cell has no field {n!r}")
+            members = [(n, dt.fields[n][0], dt.fields[n][1]) for n in names]
+        for name, kind, _ in members:
+            if kind.str not in ("<f4", "<f8"):
+                raise ValueError(f"field {name!r} is {kind}: norms reduce <f4 and <f8 fields")
+        if not 1 <= len(members) <= 8:
+            raise ValueError("norms reduce 1 to 8 fields per call")
+        if other is not None and ((other.height, other.width) != (self.height, self.width) or other.cell_dtype != dt):
+            raise ValueError("the other grid has not the same size and cell type as the grid")
+        capi.init(self.device.index if self.device.index is not None else -1)
+        with capi.on_stream(self.device) as torch_stream:
+            base = self.cells.data_ptr()
+            table = [capi.norm_field(base + offset, kind.str, dt.itemsize, self.height, self.width, rows=rows, cols=cols)
+                     for _, kind, offset in members]
+            there = None if other is None else [other.cells.data_ptr() + offset for _, _, offset in members]
+            result = capi.grid_norms(table, there, stream=torch_stream.cuda_stream)
+        return {name: Norms(r.n_cells, r.n_nonfinite, r.max_abs, r.sum, r.sum_abs, r.sum_sq)
+                for (name, _, _), r in zip(members, result)}
 
 
 @dataclass
