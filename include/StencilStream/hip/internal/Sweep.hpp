@@ -821,8 +821,14 @@ struct Sweep {
                             return TDV{};
                         else if constexpr (INLINE_TDV)
                             return fn.get_time_dependent_value(iteration);
-                        else
+                        else if constexpr (std::is_scalar_v<TDV>)
                             return launch_tdv[(level - 1) / NS];
+                        else {
+                            // a struct: its copy constructor takes no reference into the constant address space
+                            TDV value;
+                            __builtin_memcpy(&value, launch_tdv + (level - 1) / NS, sizeof(TDV));
+                            return value;
+                        }
                     }();
 
                     // rows j-R .. j+R of the previous level, widened by R cells from both neighbour lanes

@@ -127,6 +127,29 @@ static void test_split_request_on_fat_cells() {
                 same = same && std::memcmp(&x[r][c], &y[r][c], sizeof(FatCell)) == 0;
     }
     REQUIRE(same);
+    // both instantiations sweep AoS cells (SplitCellPolicy), so equal results say nothing about the sweep: the cpu
+    // backend on the same function is the reference
+    cpu::Grid<FatCell> host_grid(h, w);
+    {
+        cpu::Grid<FatCell>::GridAccessor<sycl::access::mode::read_write> hc(host_grid);
+        for (std::size_t r = 0; r < h; r++)
+            for (std::size_t c = 0; c < w; c++)
+                hc[r][c] = FatCell{float(r), float(c), float(r + c), 1.0f};
+    }
+    cpu::StencilUpdate<FatShift> reference({.transition_function = FatShift(),
+                                            .halo_value = FatCell{-1.0f, -2.0f, -3.0f, -4.0f},
+                                            .n_iterations = 11,
+                                            .blocking = true});
+    cpu::Grid<FatCell> want = reference(host_grid);
+    bool as_cpu = true;
+    {
+        hip::Grid<FatCell>::GridAccessor<sycl::access::mode::read> x(a);
+        cpu::Grid<FatCell>::GridAccessor<sycl::access::mode::read> y(want);
+        for (std::size_t r = 0; r < h; r++)
+            for (std::size_t c = 0; c < w; c++)
+                as_cpu = as_cpu && std::memcmp(&x[r][c], &y[r][c], sizeof(FatCell)) == 0;
+    }
+    REQUIRE(as_cpu);
     // zero iterations: the split path returns a fresh grid (cuda/StencilUpdate.hpp:285,440), never an alias
     split.get_params().n_iterations = 0;
     hip::Grid<FatCell> copy = split(grid);

@@ -1,0 +1,12 @@
+// Shape coverage of the template sweep, part b: the relaxed depth 6 with a struct as time-dependent value, one double per cell, the three-float cell on planes
+// (shape_cases.hpp; run by tests/test_template_shapes_gpu.py).
+#include "shape_cases.hpp"
+
+using namespace shapes;
+
+int main() {
+    run_case<F3>("F3", 0x2001u);
+    run_case<D1>("D1", 0x2002u);
+    run_case<Tri1, true>("Tri1/planes", 0x2003u);
+    return finish("shape_test_b");
+}
