@@ -7,6 +7,13 @@
 // falls would go unnoticed -- so nothing is rerouted on the strength of samples alone: the author asserts the form by
 // specialising LinearCross5<F>, and the probe only catches a declaration that does not hold in THIS build of F (a
 // different expression, other coefficients, or the same source contracted into fused multiply-adds).
+//
+// The probe compares F with the declared expression inside F's own translation unit, so what that build does to both
+// alike it cannot see that way: a build that flushes fp32 subnormals to zero (-fgpu-flush-denormals-to-zero: its
+// kernels run with the flushing denormal mode) flushes F and the declared expression alike, while the library's
+// kernels keep subnormals.  The table's last entry is therefore a sentinel whose results the host knows: a product of
+// two normal numbers that is exactly a subnormal, and a subnormal plus +0.  A build that returns zero for either is
+// not routed.
 #pragma once
 #include "../Stencil.hpp"
 #include "internal/Runtime.hpp"
@@ -85,11 +92,12 @@ struct LinearFormCoefficients {
 };
 
 constexpr int linear_form_random_samples = 4096;
-constexpr int linear_form_samples = 1 + 5 + linear_form_random_samples;
+constexpr int linear_form_samples = 1 + 5 + linear_form_random_samples + 1; // the last one is the sentinel
 constexpr std::uint64_t linear_form_seed = 0x5715C11A5EEDull;
 
 // The fixed table: the zero stencil, the five unit impulses (N, W, S, E, C), then seeded random stencils of both
-// signs and magnitudes from 2^-20 to 2^20 at varying positions and generations.
+// signs and magnitudes from 2^-20 to 2^20 at varying positions and generations; last the subnormal sentinel:
+// n * w = 2^-100 * 2^-30 is exactly the subnormal 2^-130, s + e = 2^-140 + 0 is s.
 inline std::vector<LinearFormSample> const &linear_form_table() {
     static const std::vector<LinearFormSample> table = [] {
         std::vector<LinearFormSample> t(linear_form_samples);
@@ -116,6 +124,8 @@ inline std::vector<LinearFormSample> const &linear_form_table() {
             if (i >= 1 && i <= 5) {
                 float *cell[5] = {&s.n, &s.w, &s.s, &s.e, &s.c};
                 *cell[i - 1] = 1.0f;
+            } else if (i == linear_form_samples - 1) {
+                s.n = 0x1p-100f, s.w = 0x1p-30f, s.s = 0x1p-140f, s.e = 0.0f;
             } else if (i > 5) {
                 s.n = value(), s.w = value(), s.s = value(), s.e = value(), s.c = value();
                 for (float &corner : s.corner)
@@ -153,6 +163,10 @@ __global__ void linear_form_probe_kernel(const F f, const LinearFormCoefficients
     if (i >= n_samples)
         return;
     const LinearFormSample s = samples[i];
+    if (i == n_samples - 1) { // the sentinel: the operands come from memory, so this build's kernels do the arithmetic
+        results[i] = LinearFormResult{bits_of(rounded_here(s.n * s.w)), bits_of(rounded_here(s.s + s.e))};
+        return;
+    }
     using StencilImpl = Stencil<float, 1, typename F::TimeDependentValue>;
     StencilImpl st(sycl::id<2>(s.row, s.col), sycl::range<2>(s.rows, s.cols), std::size_t(s.iteration), 0,
                    typename F::TimeDependentValue{});
@@ -174,7 +188,8 @@ __global__ void linear_form_probe_kernel(const F f, const LinearFormCoefficients
 
 // What the probe found for one (transition function, build).
 struct LinearFormVerdict {
-    bool verified = false; // F is the declared expression on every sample, the impulses return the coefficients
+    bool verified = false; // F is the declared expression on every sample, the impulses return the coefficients, and
+                           // this build keeps fp32 subnormals as the library's kernels do
     float coef[5] = {};
     const char *reason = "the linear form has not been probed"; // why not verified
 };
@@ -215,17 +230,21 @@ template <typename F> LinearFormVerdict probe_linear_form(F const &f) {
         verdict.reason = "the linear form probe could not run";
         return verdict;
     }
+    LinearFormResult const &sentinel = host[linear_form_samples - 1];
+    const bool keeps_subnormals = sentinel.function == 0x00080000u /* 2^-130 */ && sentinel.declared == 0x00000200u /* 2^-140 */;
     bool same = true;
-    for (LinearFormResult const &r : host)
-        same = same && r.function == r.declared;
+    for (int i = 0; i < linear_form_samples - 1; i++)
+        same = same && host[i].function == host[i].declared;
     bool impulses = true;
     for (int k = 0; k < 5; k++) {
         std::uint32_t declared;
         std::memcpy(&declared, &coef.c[k], sizeof declared);
         impulses = impulses && host[1 + k].function == declared;
     }
-    verdict.verified = same && impulses;
-    if (!same)
+    verdict.verified = keeps_subnormals && same && impulses;
+    if (!keeps_subnormals)
+        verdict.reason = "this build flushes fp32 subnormals";
+    else if (!same)
         verdict.reason = "the probe found the function to differ from its declared linear form in this build";
     else if (!impulses)
         verdict.reason = "the function's unit impulses do not return the declared coefficients";

@@ -5,18 +5,24 @@
 //   linear_form_test                 every case of the plain build
 //   linear_form_test knob            the routed case alone, prints "form: <name>" (run with STSTHIP_LINEAR_FORM=0)
 //   linear_form_test dump <file>     the routed case alone, prints "form: <name>" and writes the cells to <file>
+//   linear_form_test dump-tiny <file>  the same on data around the subnormal threshold
 //
-// Built twice (Makefile): with -ffp-contract=off, and as linear_form_test_fma with -ffp-contract=fast, where the
-// functor is compiled into fused multiply-adds, is no longer its declared expression, and must not be rerouted.
+// Built three times (Makefile): with -ffp-contract=off; as linear_form_test_fma with -ffp-contract=fast, where the
+// functor is compiled into fused multiply-adds, is no longer its declared expression, and must not be rerouted; and as
+// linear_form_test_ftz with -fgpu-flush-denormals-to-zero, whose kernels flush fp32 subnormals where the library's
+// keep them, and which must not be rerouted either (only its knob and dump modes are run: the cpu backend it would
+// be compared with does not flush).
 #include "../cpp/mini_test.hpp"
 #include <StencilStream/BaseTransitionFunction.hpp>
 #include <StencilStream/cpu/StencilUpdate.hpp>
 #include <StencilStream/hip/StencilUpdate.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -115,6 +121,45 @@ static Cells random_cells(std::size_t h, std::size_t w, bool both_signs, std::ui
     return cells;
 }
 
+// random sign and mantissa, exponents 2^-150 .. 2^-120 around the smallest normal 2^-126: subnormals and normals side
+// by side, in the data and in what a few generations of an averaging stencil make of them
+static Cells tiny_cells(std::size_t h, std::size_t w, std::uint64_t seed) {
+    Cells cells(h * w);
+    std::uint64_t state = seed * 0x9E3779B97F4A7C15ull + 1;
+    for (float &v : cells) {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        const float mantissa = 1.0f + float(std::uint32_t(state >> 40)) / float(1u << 24);
+        const int exponent = -150 + int((state >> 20) % 31u);
+        v = std::ldexp((state >> 10) & 1u ? -mantissa : mantissa, exponent);
+    }
+    return cells;
+}
+
+// values in (-1, 1) with a few planted cells: a NaN in the first corner, in the last column and on either side of the
+// first strip seam, a +inf with a -inf as its right neighbour (a NaN after one generation) in the last corner, in the
+// first row and across the seam, subnormals in the other corners, in the first column and right of the seam, a run of
+// -0.0 along the first row across column 64.  Without a seam
+// (`strip` = 0 or not less than the width) column 64 or the middle column stands in for it.
+static Cells planted_cells(std::size_t h, std::size_t w, std::uint64_t seed, std::size_t strip) {
+    Cells cells = random_cells(h, w, true, seed);
+    const std::size_t seam = strip > 0 && strip < w ? strip : (w > 65 ? 64 : w / 2);
+    auto at = [&](std::size_t r, std::size_t c) -> float & { return cells[r * w + c]; };
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    const float subnormal = std::numeric_limits<float>::denorm_min() * 77.0f;
+    for (std::size_t c = 1; c < std::min<std::size_t>(w / 2, 70); c++)
+        at(0, c) = -0.0f;
+    at(0, w - 1) = subnormal, at(h - 1, 0) = -subnormal;
+    if (h >= 8 && w >= 8) {
+        at(h / 2, seam - 1) = nan, at(3 * h / 4, seam) = nan, at(2 * h / 3, w - 1) = nan;
+        at(h / 4, seam) = subnormal, at(h / 2, 0) = -subnormal;
+        at(h / 3, seam - 1) = inf, at(h / 3, seam) = -inf;
+        at(0, w / 2) = inf, at(0, w / 2 + 1) = -inf;
+    }
+    at(0, 0) = nan;
+    at(h - 1, w - 2) = inf, at(h - 1, w - 1) = -inf;
+    return cells;
+}
+
 template <typename Grid> static Grid grid_of(Cells const &cells, std::size_t h, std::size_t w) {
     Grid grid(h, w);
     {
@@ -135,6 +180,30 @@ template <typename Grid> static Cells cells_of(Grid &grid, std::size_t h, std::s
 }
 static bool same_bits(Cells const &a, Cells const &b) {
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(float)) == 0;
+}
+
+// The rule for data with non-finite cells: NaNs in exactly the same cells (which NaN an operation returns differs
+// between x86 and the GPU), every other cell -- +-inf and +-0 included -- the same bits.  No tolerance.
+static bool same_cells(Cells const &a, Cells const &b) {
+    if (a.size() != b.size())
+        return false;
+    for (std::size_t i = 0; i < a.size(); i++)
+        if (std::isnan(a[i]) != std::isnan(b[i]) || (!std::isnan(a[i]) && std::memcmp(&a[i], &b[i], sizeof(float)) != 0))
+            return false;
+    return true;
+}
+struct Shares {
+    double subnormal = 0, nan = 0, finite_nonzero = 0;
+};
+static Shares shares_of(Cells const &cells) {
+    Shares s;
+    for (float v : cells) {
+        s.subnormal += std::fpclassify(v) == FP_SUBNORMAL;
+        s.nan += std::isnan(v);
+        s.finite_nonzero += std::isfinite(v) && v != 0.0f;
+    }
+    const double n = double(cells.size());
+    return {s.subnormal / n, s.nan / n, s.finite_nonzero / n};
 }
 
 // the cpu backend on the same functor
@@ -172,6 +241,34 @@ static void expect(const char *what, F const &f, float halo, std::size_t h, std:
     REQUIRE(right_cells);
 }
 
+// the same on tiny or planted data, by the rule of same_cells; the cpu backend's result must hold the cells the data is
+// there for (at least 1 % subnormals or NaNs, at most half NaNs, at least 10 % finite and not zero)
+template <typename F>
+static void expect_special(const char *what, F const &f, std::size_t h, std::size_t w, std::size_t n, bool planted,
+                           hip::SweepForm form) {
+    hip::StencilUpdate<F> update({.transition_function = f, .halo_value = 0.0f, .n_iterations = n, .blocking = true});
+    std::size_t strip = hip::StencilUpdate<F>::sweep_description().strip_width;
+    ststhip_app_info info;
+    if (form == hip::SweepForm::jacobi5_uniform && ststhip_app_find("jacobi5uniform", &info) == STSTHIP_OK)
+        strip = info.strip_width;
+    const std::uint64_t seed = h * 1000003 + w * 101 + n;
+    const Cells cells = planted ? planted_cells(h, w, seed, strip) : tiny_cells(h, w, seed);
+    const Cells got = on_hip(update, cells, h, w);
+    const Cells want = on_cpu(f, 0.0f, cells, h, w, 0, n);
+    const Shares shares = shares_of(want);
+    const bool right_form = update.get_sweep_form() == form, right_cells = same_cells(got, want);
+    const bool telling = (planted ? shares.nan : shares.subnormal) >= 0.01 && shares.nan <= 0.5 && shares.finite_nonzero >= 0.1;
+    if (!right_form || !right_cells || !telling)
+        std::fprintf(stderr, "%s %zu x %zu, %zu generations, %s data (%.1f %% subnormal, %.1f %% NaN, %.1f %% finite and not "
+                             "zero): form %s (expected %s), cells %s\n",
+                     what, h, w, n, planted ? "planted" : "tiny", 100 * shares.subnormal, 100 * shares.nan,
+                     100 * shares.finite_nonzero, to_string(update.get_sweep_form()), to_string(form),
+                     right_cells ? "equal" : "DIFFER from the cpu backend");
+    REQUIRE(right_form);
+    REQUIRE(right_cells);
+    REQUIRE(telling);
+}
+
 static const UserCross5 uniform_cross{.coef = {0.2f, 0.2f, 0.2f, 0.2f, 0.2f}};
 static const UserCross5 distinct_cross{.coef = {0.2f, 0.21f, 0.19f, 0.22f, 0.18f}};
 
@@ -184,6 +281,13 @@ static void test_routed() {
             for (bool both_signs : {false, true})
                 expect("UserCross5 0.2 x 5", uniform_cross, 0.0f, shape[0], shape[1], n, both_signs,
                        hip::SweepForm::jacobi5_uniform);
+    // subnormals, signed zeros, infinities and NaNs: the products the form carries go subnormal or infinite exactly
+    // where the declared expression does
+    for (std::size_t s = 0; s < 2; s++)
+        for (std::size_t n : {17, 37})
+            for (bool planted : {false, true})
+                expect_special("UserCross5 0.2 x 5", uniform_cross, shapes[s][0], shapes[s][1], n, planted,
+                               hip::SweepForm::jacobi5_uniform);
 }
 
 static void test_not_routed() {
@@ -197,6 +301,11 @@ static void test_not_routed() {
     // (a clamp that bites: cells above 0.9 exist after one generation of 0.3 x 5 on [0, 1))
     expect("Clamped5 0.3 x 5", Clamped5{.coef = {0.3f, 0.3f, 0.3f, 0.3f, 0.3f}}, 0.0f, 130, 257, 17, false, general);
     expect("Undeclared5", Undeclared5{.coef = {0.2f, 0.2f, 0.2f, 0.2f, 0.2f}}, 0.0f, 130, 257, 17, false, general);
+    for (std::size_t n : {17, 37})
+        for (bool planted : {false, true}) {
+            expect_special("UserCross5 distinct", distinct_cross, 130, 257, n, planted, general);
+            expect_special("UserCross5 distinct", distinct_cross, 300, 700, n, planted, general);
+        }
 }
 
 // 20 generations, then 17 more from generation 20 on the same object: one call of 37
@@ -238,10 +347,10 @@ static void test_parameter_change() {
     REQUIRE(update.get_sweep_form() == hip::SweepForm::general);
 }
 
-// the routed case on its own: 300 x 700, 37 generations, both signs
-static int routed_case_alone(const char *path) {
+// the routed case on its own: 300 x 700, 37 generations, both signs or tiny data
+static int routed_case_alone(const char *path, bool tiny = false) {
     const std::size_t h = 300, w = 700;
-    const Cells cells = random_cells(h, w, true, 37);
+    const Cells cells = tiny ? tiny_cells(h, w, 37) : random_cells(h, w, true, 37);
     hip::StencilUpdate<UserCross5> update({.transition_function = uniform_cross, .halo_value = 0.0f, .n_iterations = 37,
                                            .blocking = true});
     const Cells got = on_hip(update, cells, h, w);
@@ -261,8 +370,10 @@ int main(int argc, char **argv) {
         return routed_case_alone(nullptr);
     if (mode == "dump" && argc > 2)
         return routed_case_alone(argv[2]);
+    if (mode == "dump-tiny" && argc > 2)
+        return routed_case_alone(argv[2], true);
     if (mode != "all") {
-        std::fprintf(stderr, "usage: %s [all | knob | dump <file>]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [all | knob | dump <file> | dump-tiny <file>]\n", argv[0]);
         return 2;
     }
     test_routed();

@@ -1,8 +1,8 @@
 """Declared linear five-point functors (include/StencilStream/hip/LinearForm.hpp): a functor that declares
 stencil::hip::LinearCross5 and passes the device-side probe is swept by the product-carrying form of the five-point
 Jacobi where its coefficients and halo allow it, with the cpu backend's cells bit for bit; everything else runs the
-general sweep as before.  Drives tests/cpp_forms/linear_form_test.hip (plain and -ffp-contract=fast builds) and the
-reference's unchanged Jacobi example."""
+general sweep as before.  Drives tests/cpp_forms/linear_form_test.hip (plain, -ffp-contract=fast and
+-fgpu-flush-denormals-to-zero builds) and the reference's unchanged Jacobi example."""
 import os
 import subprocess
 
@@ -44,7 +44,8 @@ def run(cmd, **env):
 def test_forms_and_cells_of_every_case(env):
     """Every case of the plain build: UserCross5 with 0.2 x 5 and a +0 halo runs jacobi5_uniform on 300 x 700,
     130 x 257, 3 x 5 and 1 x 1 for 1, 2, 16, 17 and 37 generations (only / first / middle / last launch kernels), on
-    data in [0, 1) and of both signs; distinct or negative coefficients, other halos, a functor that lies about its
+    data in [0, 1) and of both signs, and for 17 and 37 generations on data around the subnormal threshold and on data
+    with planted NaN, +-inf, subnormal and -0.0 cells (there: NaNs in the same cells, all other cells equal); distinct or negative coefficients, other halos, a functor that lies about its
     form, a clamped one and an undeclared one run general; resuming at generation 20 and changing the parameters
     through get_params() follow.  All cells equal stencil::cpu::StencilUpdate on the same functor."""
     res = run([binary("linear_form_test")], **env)
@@ -77,6 +78,32 @@ def test_contracted_build_is_never_changed_by_the_route(tmp_path, env):
     if b"form: jacobi5_uniform" in res.stdout:
         run([binary("linear_form_test"), "dump", str(plain)], **env)
         assert np.array_equal(got, np.fromfile(plain, dtype=np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [{}, WIDE], ids=["narrow-lanes", "four-cells-per-lane"])
+def test_flushing_build_is_never_changed_by_the_route(tmp_path, env):
+    """linear_form_test_ftz (-fgpu-flush-denormals-to-zero: its kernels flush fp32 subnormals, the library's keep them)
+    on data around the subnormal threshold: its cells with and without STSTHIP_LINEAR_FORM=0 are the same bits
+    whichever form it reports, and the trace names the reason; a build that reports the uniform form must also give
+    the plain build's cells.  Its `all` mode is not run: the cpu backend does not flush."""
+    routed, kept, plain = tmp_path / "routed.bin", tmp_path / "kept.bin", tmp_path / "plain.bin"
+    res = run([binary("linear_form_test_ftz"), "dump-tiny", str(routed)], STSTHIP_TRACE_FORM="1", **env)
+    run([binary("linear_form_test_ftz"), "dump-tiny", str(kept)], STSTHIP_LINEAR_FORM="0", **env)
+    run([binary("linear_form_test"), "dump-tiny", str(plain)], **env)
+    got, want = np.fromfile(routed, dtype=np.uint32), np.fromfile(kept, dtype=np.uint32)
+    unflushed = np.fromfile(plain, dtype=np.uint32)
+    # the data is telling: a third of the plain build's cells are subnormal, a flushing kernel cannot return them
+    subnormal = ((unflushed & 0x7F800000) == 0) & ((unflushed & 0x007FFFFF) != 0)
+    print(f"subnormal cells of the plain build: {subnormal.mean():.3f}; {res.stdout.decode().strip()}; "
+          f"routed and kept differ in {(got != want).sum()} cells")
+    assert unflushed.size == 300 * 700 and subnormal.mean() >= 0.1
+    assert got.size == 300 * 700 and np.array_equal(got, want)
+    assert b"form: " in res.stdout
+    if b"form: jacobi5_uniform" in res.stdout:
+        assert np.array_equal(got, unflushed)
+    else:
+        assert b"sweep form: general (this build flushes fp32 subnormals)" in res.stderr, res.stderr.decode()[-2000:]
 
 
 @pytest.mark.gpu
