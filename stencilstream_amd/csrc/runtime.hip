@@ -2,7 +2,9 @@
 //
 // Layer 0: device selection, one runtime stream, a size-bucketed HBM pool, pinned host memory,
 // async copies, events, kernel launch, LDS-staged AoS<->planes transforms, RCCL ghost-row exchange.
-// Layer 1: registry and drivers for the precompiled transition functions (app_*.hip).
+// Layer 1: registry and drivers for the precompiled transition functions (app_*.hip).  The three drivers that enqueue
+// launches (ststhip_run_passes, ststhip_strip_advance, block_advance) share LaunchState (with its guard), OrderKit,
+// ValuesTable and MovingBoundary; strips and blocks share their creation helpers.
 #include "app_registry.hpp"
 
 #include <dlfcn.h>
@@ -12,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <numeric>
@@ -909,58 +912,137 @@ int ststhip_occupancy(const void *function, unsigned block_threads, size_t share
     return STSTHIP_OK;
 }
 
-static thread_local const void *g_tdv_table = nullptr;
-static thread_local std::uint64_t g_tdv_first = 0, g_tdv_count = 0, g_tdv_size = 0;
+} // extern "C"
+
+// ------------------------------------------------------------------ what the drivers share
+// The helpers of the three drivers (ststhip_run_passes, ststhip_strip_advance, block_advance): LaunchState, OrderKit,
+// ValuesTable and MovingBoundary.  Plain structs and inline functions: nothing here allocates per pass or per launch.
+namespace {
+// What a sweep callback may ask about the launch it is called for (ststhip.h, ststhip_launch_concurrency ...
+// ststhip_launch_columns), per host thread.  A default-constructed one is the idle state between driver calls.
+struct LaunchState {
+    const void *tdv_table = nullptr; // the call's table of time-dependent values: base, first generation, values, bytes each
+    std::uint64_t tdv_first = 0, tdv_count = 0, tdv_size = 0;
+    int concurrency = 1;
+    int target_holds_constants = 0;
+    std::uint64_t row_hole_begin = 0, row_hole_end = 0;
+    std::uint64_t col_begin = 0, col_end = 0;
+};
+thread_local LaunchState g_launch;
+// (an entry point's answer into an argument that may be null)
+template <typename T> int put(T *to, T value) {
+    if (to)
+        *to = value;
+    return STSTHIP_OK;
+}
+// Declared by a driver before it first touches the state: every way out of the driver leaves the thread idle, whatever
+// the state was before (a caller's ststhip_set_launch_concurrency included).
+struct LaunchStateGuard {
+    ~LaunchStateGuard() { g_launch = LaunchState{}; }
+};
+
+// The orderings of one driver call: events from the pool, and the call's status.  Events and stream waits carry the
+// ordering between streams, so a failure there must fail the call: the first one is latched with the name of its call.
+struct OrderKit {
+    EventPool events;
+    int rc = STSTHIP_OK;
+    void ordered(hipError_t err, const char *what) {
+        if (err != hipSuccess && rc == STSTHIP_OK)
+            rc = hip_fail(err, what);
+    }
+    // everything queued on `on` so far
+    hipEvent_t record(hipStream_t on) {
+        hipEvent_t ev = events.take();
+        if (!ev)
+            ordered(hipErrorUnknown, "hipEventCreateWithFlags");
+        else
+            ordered(hipEventRecord(ev, on), "hipEventRecord");
+        return ev;
+    }
+    void wait(hipStream_t who, hipEvent_t ev) {
+        if (ev)
+            ordered(hipStreamWaitEvent(who, ev, 0), "hipStreamWaitEvent");
+    }
+    // `into` continues after everything queued so far on each of `streams` (a null one is a stream the call does not use)
+    void join(hipStream_t into, const hipStream_t *first, const hipStream_t *last) {
+        for (; first != last; ++first)
+            if (*first)
+                wait(into, record(*first));
+    }
+    void join(hipStream_t into, std::initializer_list<hipStream_t> streams) { join(into, streams.begin(), streams.end()); }
+};
+
+// One device table of time-dependent values for a whole driver call (ststhip_sweep_desc::fill_tdv), published in the
+// launch state; a table the caller keeps on the device (`device_table`, the pass driver only) is published as it is.
+struct ValuesTable {
+    void *owned = nullptr;
+    void open(const ststhip_sweep_desc &d, void *ctx, std::uint64_t offset, std::uint64_t n, hipStream_t stream, OrderKit &kit,
+              const void *device_table = nullptr) {
+        if (kit.rc != STSTHIP_OK || d.tdv_size == 0 || !(d.fill_tdv || device_table))
+            return;
+        if (!device_table) {
+            const std::size_t bytes = std::size_t(d.tdv_size) * n;
+            if ((kit.rc = ststhip_malloc_async(&owned, bytes, stream)) != STSTHIP_OK)
+                return;
+            std::vector<unsigned char> values(bytes);
+            d.fill_tdv(ctx, offset, n, values.data());
+            // `values` is pageable and goes out of scope: the copy must have read it before that
+            kit.ordered(hipMemcpyAsync(owned, values.data(), bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+            kit.ordered(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        }
+        g_launch.tdv_table = device_table ? device_table : owned;
+        g_launch.tdv_first = offset;
+        g_launch.tdv_count = n;
+        g_launch.tdv_size = d.tdv_size;
+    }
+    // on the stream every other stream of the call has been joined into, after the joins are enqueued -- no destructor:
+    // a free in front of them would hand the block on too early
+    void close(hipStream_t stream) {
+        if (owned)
+            ststhip_free_async(owned, stream);
+        owned = nullptr;
+    }
+};
+
+// The common boundaries of strips that move UP by a launch's ghost rows from pass to pass (ststhip_run_passes, the
+// skewed pass): `offset` is how far below their highest places they are.  When they have moved a span they start over.
+struct MovingBoundary {
+    std::uint64_t span = 0, offset = 0, g_before = 0;
+    // the pass of `g` ghost rows moves them by the larger of its own and the ones of the pass before; true: they start over
+    bool step(std::uint64_t g) {
+        const std::uint64_t shift = std::max(g, g_before);
+        g_before = g;
+        if (offset + shift > span) {
+            offset = 0;
+            return true;
+        }
+        offset += shift;
+        return false;
+    }
+};
+} // namespace
+
+extern "C" {
+
 int ststhip_current_tdv_table(const void **base, uint64_t *first_iteration, uint64_t *n_values,
                               uint64_t *value_size) {
-    if (base)
-        *base = g_tdv_table;
-    if (first_iteration)
-        *first_iteration = g_tdv_first;
-    if (n_values)
-        *n_values = g_tdv_count;
-    if (value_size)
-        *value_size = g_tdv_size;
-    return STSTHIP_OK;
+    put(base, g_launch.tdv_table), put(first_iteration, g_launch.tdv_first), put(n_values, g_launch.tdv_count);
+    return put(value_size, g_launch.tdv_size);
 }
-
-static thread_local int g_launch_concurrency = 1;
-static thread_local int g_target_holds_constants = 0;
-int ststhip_launch_concurrency(void) { return g_launch_concurrency; }
-static thread_local std::uint64_t g_row_hole_begin = 0, g_row_hole_end = 0;
-int ststhip_launch_row_hole(uint64_t *begin, uint64_t *end) {
-    if (begin)
-        *begin = g_row_hole_begin;
-    if (end)
-        *end = g_row_hole_end;
-    return STSTHIP_OK;
-}
+int ststhip_launch_concurrency(void) { return g_launch.concurrency; }
+int ststhip_set_launch_concurrency(int n) { return (g_launch.concurrency = std::min(std::max(n, 1), 8), STSTHIP_OK); }
+int ststhip_target_holds_constants(void) { return g_launch.target_holds_constants; }
+int ststhip_launch_row_hole(uint64_t *begin, uint64_t *end) { return put(begin, g_launch.row_hole_begin), put(end, g_launch.row_hole_end); }
 int ststhip_set_launch_row_hole(uint64_t begin, uint64_t end) {
     if (begin > end)
         return fail(STSTHIP_ERR_INVALID, "row hole: begin after end");
-    g_row_hole_begin = begin;
-    g_row_hole_end = end;
-    return STSTHIP_OK;
+    return (g_launch.row_hole_begin = begin, g_launch.row_hole_end = end, STSTHIP_OK);
 }
-static thread_local std::uint64_t g_col_begin = 0, g_col_end = 0;
-int ststhip_launch_columns(uint64_t *begin, uint64_t *end) {
-    if (begin)
-        *begin = g_col_begin;
-    if (end)
-        *end = g_col_end;
-    return STSTHIP_OK;
-}
+int ststhip_launch_columns(uint64_t *begin, uint64_t *end) { return put(begin, g_launch.col_begin), put(end, g_launch.col_end); }
 int ststhip_set_launch_columns(uint64_t begin, uint64_t end) {
     if (end < begin)
         return fail(STSTHIP_ERR_INVALID, "bad column range");
-    g_col_begin = begin;
-    g_col_end = end;
-    return STSTHIP_OK;
-}
-int ststhip_target_holds_constants(void) { return g_target_holds_constants; }
-int ststhip_set_launch_concurrency(int n) {
-    g_launch_concurrency = std::min(std::max(n, 1), 8);
-    return STSTHIP_OK;
+    return (g_launch.col_begin = begin, g_launch.col_end = end, STSTHIP_OK);
 }
 
 // Two row strips (two launches side by side, their boundary bands beside them on streams of their own) against one
@@ -1137,7 +1219,7 @@ static int check_domain(const AppEntry *e, const ststhip_domain *dom, std::uint6
         const std::int64_t held_lo = std::max<std::int64_t>(0, dom->col_origin);
         const std::int64_t held_hi = std::min<std::int64_t>(std::int64_t(dom->global_width),
                                                             dom->col_origin + std::int64_t(dom->local_cols));
-        std::int64_t cb = std::int64_t(g_col_begin), ce = std::int64_t(g_col_end);
+        std::int64_t cb = std::int64_t(g_launch.col_begin), ce = std::int64_t(g_launch.col_end);
         if (cb == ce) {
             cb = held_lo;
             ce = held_hi;
@@ -1295,6 +1377,231 @@ int ststhip_app_tuned_depth(const char *app, uint64_t height, uint64_t width, ui
     return ststhip_tuned_depth(reinterpret_cast<std::uintptr_t>(e), height, width, depth);
 }
 
+namespace {
+// What one ststhip_run_passes call and the parts of it that are functions of their own share.
+struct PassCall {
+    // what the caller asked for
+    ststhip_sweep_fn sweep;
+    void *ctx;
+    const ststhip_sweep_desc *desc;
+    const ststhip_domain *dom;
+    const void *const *src;
+    void *const *dst;
+    std::uint64_t iteration_offset;
+    hipStream_t s; // the caller's stream
+    std::chrono::high_resolution_clock::time_point started;
+    // the plan: passes of the whole call, and the tiles behind an arriving source (depth, ghost rows, passes at most,
+    // and what their number must be a multiple of)
+    std::size_t total_passes;
+    std::uint32_t tile_depth;
+    std::uint64_t tile_g;
+    std::uint32_t quantum;
+    std::uint64_t stream_limit;
+    // the call's own
+    OrderKit kit;
+    std::uint64_t n_launches = 0;
+    void *scratch[16] = {nullptr};
+    // row strips: their streams (strip 0 on the caller's), rows [bound[v], bound[v + 1]), and with boundary bands the
+    // bands' streams and, per strip, the events of the bands and of the interior of the previous pass
+    int strips = 1;
+    std::vector<hipStream_t> lane, band_lane;
+    bool bands_beside = false;
+    std::vector<std::uint64_t> bound;
+    std::vector<hipEvent_t> bands_done, interior_done;
+    // which planes pass k of the call writes: the last one `dst`, alternating backwards from there
+    void *const *target_of(std::uint64_t k) { return ((total_passes - 1 - k) % 2) == 0 ? dst : scratch; }
+};
+
+// The passes behind a source that is still arriving (ststhip.h, ststhip_set_source_arrival); returns how many ran.
+// frontier[p] = rows [0, frontier[p]) of pass p are done (or queued).  When block k has arrived, rows
+// [0, end_k) of the source are there and pass p may advance to end_k - (p + 1) * g: a tile of pass p reads g rows
+// beyond its own on both sides in the output of pass p - 1, and pass p - 1 has come g rows further.  The tiles of
+// one block (its "column": p = 0, 1, ...) form a chain on one stream; the columns of consecutive blocks run on
+// different streams, one pass apart (a tile waits for the tiles of the pass before it that overlap what it
+// reads -- the same tiles are the last readers of the rows it overwrites, two passes share a buffer set).
+std::uint64_t passes_behind_source(PassCall &c, const std::vector<ststhip_source_block> &arrival) {
+    OrderKit &kit = c.kit;
+    int &rc = kit.rc;
+    const std::uint64_t H = c.dom->global_height;
+    std::uint64_t streamed = 0;
+    struct Tile {
+        std::uint64_t begin, end;
+        hipEvent_t done;
+        hipStream_t on;
+    };
+    std::vector<hipStream_t> tile_lane(1, c.s), extra;
+    if (side_streams_for(c.s, 1, extra))
+        tile_lane.push_back(extra[0]);
+    {
+        // (the scratch planes were allocated for work on the caller's stream)
+        hipEvent_t begin = kit.record(c.s);
+        for (std::size_t v = 1; v < tile_lane.size(); v++)
+            kit.wait(tile_lane[v], begin);
+    }
+    std::vector<std::vector<Tile>> tiles(c.stream_limit);
+    std::vector<std::uint64_t> frontier(c.stream_limit, 0);
+    // How deep a column goes: as deep as it takes to keep the chip busy until the next block is there -- and a
+    // little busier: a tile of one block's rows cannot fill the chip on its own (a 2048 x 16384 tile of the
+    // Jacobi example runs at 57 % of the whole grid's rate), two columns side by side do better, so the aim is ONE
+    // or two earlier columns still running when a block arrives.  None: the chip has idled, and the column
+    // before is timed against the blocks' arrival; three or more: the chip is behind, the next column goes
+    // less deep (passes that are begun are completed by the last column whatever the later columns did).
+    std::uint64_t row_bytes_all_planes = 0;
+    for (unsigned p = 0; p < c.desc->n_planes; p++)
+        row_bytes_all_planes += c.dom->pitch * c.desc->plane_elem_size[p];
+    std::uint64_t deep_now = std::min<std::uint64_t>(c.stream_limit, 16);
+    deep_now = std::max<std::uint64_t>(deep_now - deep_now % c.quantum, c.quantum);
+    std::uint64_t deepest = 0;
+    std::vector<hipEvent_t> clocks; // timing events of the columns: begin, end
+    g_launch.concurrency = 2;
+    const bool narrate = std::getenv("STSTHIP_TRACE_STREAM") != nullptr; // (a debugging aid: host times to stderr)
+    auto host_ms = [&] {
+        return std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - c.started).count();
+    };
+    for (std::size_t k = 0; k < arrival.size() && rc == STSTHIP_OK; k++) {
+        const double waiting_since = host_ms();
+        kit.ordered(hipEventSynchronize(static_cast<hipEvent_t>(arrival[k].ready)), "hipEventSynchronize");
+        if (rc != STSTHIP_OK)
+            break;
+        const bool last = k + 1 == arrival.size();
+        int behind = 0; // earlier columns that are still running
+        for (std::size_t j = 0; j < k; j++)
+            behind += event_done(clocks[2 * j + 1]) ? 0 : 1;
+        if (narrate)
+            std::fprintf(stderr, "[ststhip] block %zu: host waited from %.2f to %.2f ms of the call, %d columns running", k,
+                         waiting_since, host_ms(), behind);
+        if (k > 0 && !last) {
+            std::uint64_t want = deep_now;
+            if (behind == 0) {
+                // t = what a tile of the column before took (alone, or beside the one before it: the estimate
+                // is then on the careful side); two columns side by side finish a tile every 0.8 t
+                // (a block's time over PCIe by its bytes at 55 GB/s: the gaps between the arrival events are no
+                // measure -- the first blocks of an upload have been seen to arrive 5-6 ms ahead of the rest)
+                float column_ms = 0.0f;
+                const double block_ms = double(std::min(arrival[k].row_end, H) - std::min(arrival[k - 1].row_end, H)) *
+                                        double(row_bytes_all_planes) / 55e6;
+                double grow = 1.25;
+                if (hipEventElapsedTime(&column_ms, clocks[2 * (k - 1)], clocks[2 * (k - 1) + 1]) == hipSuccess &&
+                    column_ms > 0.0f)
+                    grow = std::min(4.0, std::max(1.25, block_ms / (0.8 * double(column_ms))));
+                if (narrate)
+                    std::fprintf(stderr, " (column before: %.2f ms, block: %.2f ms)", column_ms, block_ms);
+                want = std::uint64_t(double(deep_now) * grow + 0.5);
+            } else if (behind >= 3) {
+                want = deep_now * 3 / 4;
+            }
+            want -= want % c.quantum;
+            deep_now = std::min(std::max<std::uint64_t>(want, c.quantum), c.stream_limit);
+        }
+        deepest = std::max(deepest, deep_now);
+        const std::uint64_t arrived = last ? H : std::min(arrival[k].row_end, H);
+        hipStream_t on = tile_lane[k % tile_lane.size()];
+        hipEvent_t c0 = nullptr, c1 = nullptr;
+        kit.ordered(hipEventCreate(&c0), "hipEventCreate");
+        kit.ordered(hipEventCreate(&c1), "hipEventCreate");
+        clocks.push_back(c0);
+        clocks.push_back(c1);
+        if (rc != STSTHIP_OK)
+            break;
+        kit.ordered(hipEventRecord(c0, on), "hipEventRecord");
+        // (the last column completes every pass that was begun)
+        for (std::uint64_t p = 0; p < (last ? deepest : deep_now) && rc == STSTHIP_OK; p++) {
+            const std::uint64_t above = p == 0 ? arrived : frontier[p - 1];
+            const std::uint64_t upto = above >= H ? H : (above > c.tile_g ? above - c.tile_g : 0);
+            if (upto <= frontier[p])
+                break;
+            const std::uint64_t from_row = frontier[p];
+            if (p > 0)
+                for (Tile const &t : tiles[p - 1])
+                    if (t.on != on && t.end + c.tile_g > from_row && t.begin < upto + c.tile_g)
+                        kit.wait(on, t.done);
+            g_launch.target_holds_constants = p >= 2 ? 1 : 0;
+            rc = c.sweep(c.ctx, c.dom, p == 0 ? c.src : const_cast<const void *const *>(c.target_of(p - 1)), c.target_of(p),
+                         from_row, upto, c.iteration_offset + p * c.tile_depth, c.tile_depth, on);
+            c.n_launches++;
+            Tile t{from_row, upto, kit.record(on), on};
+            tiles[p].push_back(t);
+            frontier[p] = upto;
+        }
+        kit.ordered(hipEventRecord(c1, on), "hipEventRecord");
+        if (narrate)
+            std::fprintf(stderr, ", column of %llu passes queued by %.2f ms\n",
+                         (unsigned long long)(last ? deepest : deep_now), host_ms());
+        if (last)
+            streamed = deepest;
+    }
+    kit.join(c.s, tile_lane.data() + 1, tile_lane.data() + tile_lane.size());
+    if (narrate && rc == STSTHIP_OK && hipStreamSynchronize(c.s) == hipSuccess) {
+        for (std::size_t k = 0; 2 * k + 1 < clocks.size(); k++) {
+            float ms = 0.0f, since = 0.0f;
+            (void)hipEventElapsedTime(&ms, clocks[2 * k], clocks[2 * k + 1]);
+            (void)hipEventElapsedTime(&since, clocks[0], clocks[2 * k]);
+            std::fprintf(stderr, "[ststhip] column %zu ran from %.2f for %.2f ms\n", k, since, ms);
+        }
+        std::fprintf(stderr, "[ststhip] streamed passes done at %.2f ms of the call\n", host_ms());
+    }
+    for (hipEvent_t ev : clocks)
+        if (ev)
+            (void)hipEventDestroy(ev);
+    // every pass that was begun is complete now (the last block's column took each of them to the last row)
+    for (std::uint64_t p = 0; p < streamed && rc == STSTHIP_OK; p++)
+        if (frontier[p] != H)
+            rc = fail(STSTHIP_ERR_INVALID, "internal: a streamed pass is incomplete");
+    return streamed;
+}
+
+// One pass of `depth` generations (`g` ghost rows) as row strips with boundary bands: see the dependencies at
+// ststhip_run_passes, where the band streams are taken.  One strip: one launch.
+void band_pass(PassCall &c, const void *const *from, void *const *to, std::uint64_t iteration, std::uint32_t depth, std::uint64_t g) {
+    OrderKit &kit = c.kit;
+    int &rc = kit.rc;
+    std::vector<hipEvent_t> bands_now(c.strips, nullptr), interior_now(c.strips, nullptr);
+    for (int v = 0; v < c.strips && rc == STSTHIP_OK; v++) {
+        const std::uint64_t a = c.bound[v], b = c.bound[v + 1];
+        if (c.strips == 1) {
+            rc = c.sweep(c.ctx, c.dom, from, to, a, b, iteration, depth, c.lane[v]);
+            c.n_launches++;
+            continue;
+        }
+        hipStream_t bands_on = c.bands_beside ? c.band_lane[v] : c.lane[v];
+        // bands read the neighbours' bands of the previous pass (and will overwrite rows
+        // the neighbours' previous bands read): wait for them
+        if (v > 0)
+            kit.wait(bands_on, c.bands_done[v - 1]);
+        if (v + 1 < c.strips)
+            kit.wait(bands_on, c.bands_done[v + 1]);
+        if (c.bands_beside)
+            kit.wait(bands_on, c.interior_done[v]);
+        const std::uint64_t top_end = (v > 0) ? std::min(a + g, b) : a;
+        const std::uint64_t bot_begin = (v + 1 < c.strips) ? std::max(b - std::min(g, b - a), top_end) : b;
+        if (top_end > a) {
+            rc = c.sweep(c.ctx, c.dom, from, to, a, top_end, iteration, depth, bands_on);
+            c.n_launches++;
+        }
+        if (rc == STSTHIP_OK && bot_begin < b) {
+            rc = c.sweep(c.ctx, c.dom, from, to, bot_begin, b, iteration, depth, bands_on);
+            c.n_launches++;
+        }
+        bands_now[v] = kit.record(bands_on);
+        if (c.bands_beside) {
+            // the interior reads this strip's previous bands, and -- when this pass is shallower than the
+            // previous one -- overwrites rows next to them that the neighbours' previous bands read
+            for (int w = std::max(v - 1, 0); w <= std::min(v + 1, c.strips - 1); w++)
+                kit.wait(c.lane[v], c.bands_done[w]);
+        }
+        if (rc == STSTHIP_OK && top_end < bot_begin) {
+            rc = c.sweep(c.ctx, c.dom, from, to, top_end, bot_begin, iteration, depth, c.lane[v]);
+            c.n_launches++;
+        }
+        if (c.bands_beside) {
+            interior_now[v] = kit.record(c.lane[v]);
+        }
+    }
+    c.bands_done.swap(bands_now);
+    c.interior_done.swap(interior_now);
+}
+} // namespace
+
 int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_desc *desc,
                        const ststhip_domain *dom, const void *const *src, void *const *dst,
                        uint64_t iteration_offset, uint64_t n_iterations, int blocking, int profiling,
@@ -1318,6 +1625,7 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
     }
     if (int rc = ststhip_init(-1))
         return rc;
+    LaunchStateGuard idle_on_return;
     hipStream_t s = resolve(stream);
     const unsigned n_planes = desc->n_planes;
     const std::size_t plane_cells = std::size_t(dom->local_rows) * dom->pitch;
@@ -1420,27 +1728,23 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
     }
     hipEvent_t probe_events[3] = {nullptr, nullptr, nullptr};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
-    EventPool sync_events;
-    std::uint64_t n_launches = 0;
-    int rc = STSTHIP_OK;
-    void *scratch[16] = {nullptr};
-    void *tdv_table = nullptr;
-    // events and stream waits carry the ordering between strips: a failure there must fail the run
-    auto ordered = [&](hipError_t err, const char *what) {
-        if (err != hipSuccess && rc == STSTHIP_OK)
-            rc = hip_fail(err, what);
-    };
+    PassCall c{.sweep = sweep, .ctx = ctx, .desc = desc, .dom = dom, .src = src, .dst = dst, .iteration_offset = iteration_offset,
+               .s = s, .started = started, .total_passes = total_passes, .tile_depth = tile_depth, .tile_g = tile_g,
+               .quantum = quantum, .stream_limit = stream_limit};
+    OrderKit &kit = c.kit;
+    int &rc = kit.rc;
+    ValuesTable values;
 
     // how many virtual strips: only worth it for grids with many rows per strip
     const std::uint64_t g_max = std::uint64_t((!probing && depth_cap) ? std::min(deep, depth_cap) : deep) *
                                 desc->halo_depth_per_generation;
-    int strips = profiling ? 1
-                           : suggest_row_strips(H, dom->global_width, desc->strip_width, g_max, depths.size());
+    int &strips = c.strips;
+    strips = profiling ? 1 : suggest_row_strips(H, dom->global_width, desc->strip_width, g_max, depths.size());
 
     // a source in blocks that this call does not follow block by block: everything waits for all of it
     if (stream_limit == 0)
         for (auto const &blk : arrival)
-            ordered(hipStreamWaitEvent(s, static_cast<hipEvent_t>(blk.ready), 0), "hipStreamWaitEvent");
+            kit.ordered(hipStreamWaitEvent(s, static_cast<hipEvent_t>(blk.ready), 0), "hipStreamWaitEvent");
     std::uint64_t streamed = 0; // passes that ran behind the arriving source
 
     if (depths.empty()) {
@@ -1449,206 +1753,41 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
     } else {
         if (depths.size() > 1)
             for (unsigned p = 0; p < n_planes && rc == STSTHIP_OK; p++)
-                rc = ststhip_malloc_async(&scratch[p], plane_cells * desc->plane_elem_size[p], s);
+                rc = ststhip_malloc_async(&c.scratch[p], plane_cells * desc->plane_elem_size[p], s);
 
-        // one device table of time-dependent values for the whole call
-        if (rc == STSTHIP_OK && desc->tdv_size > 0 && (desc->fill_tdv || desc->tdv_device_table)) {
-            const std::size_t bytes = std::size_t(desc->tdv_size) * n_iterations;
-            if (desc->tdv_device_table) {
-                g_tdv_table = desc->tdv_device_table;
-            } else {
-                rc = ststhip_malloc_async(&tdv_table, bytes, s);
-                if (rc == STSTHIP_OK) {
-                    std::vector<unsigned char> values(bytes);
-                    desc->fill_tdv(ctx, iteration_offset, n_iterations, values.data());
-                    // `values` is pageable and goes out of scope: the copy must have read it before that
-                    ordered(hipMemcpyAsync(tdv_table, values.data(), bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync");
-                    ordered(hipStreamSynchronize(s), "hipStreamSynchronize");
-                    g_tdv_table = tdv_table;
-                }
-            }
-            g_tdv_first = iteration_offset;
-            g_tdv_count = n_iterations;
-            g_tdv_size = desc->tdv_size;
-        }
-        auto new_event = [&]() {
-            hipEvent_t e = sync_events.take();
-            if (!e)
-                ordered(hipErrorUnknown, "hipEventCreateWithFlags");
-            return e;
-        };
-        // which planes pass k of the call writes: the last one `dst`, alternating backwards from there
-        auto target_of = [&](std::uint64_t k) -> void *const * {
-            return ((total_passes - 1 - k) % 2) == 0 ? dst : scratch;
-        };
+        values.open(*desc, ctx, iteration_offset, n_iterations, s, kit, desc->tdv_device_table);
 
-        // ---- passes behind a source that is still arriving (ststhip.h, ststhip_set_source_arrival) ----
-        // frontier[p] = rows [0, frontier[p]) of pass p are done (or queued).  When block k has arrived, rows
-        // [0, end_k) of the source are there and pass p may advance to end_k - (p + 1) * g: a tile of pass p reads g rows
-        // beyond its own on both sides in the output of pass p - 1, and pass p - 1 has come g rows further.  The tiles of
-        // one block (its "column": p = 0, 1, ...) form a chain on one stream; the columns of consecutive blocks run on
-        // different streams, one pass apart (a tile waits for the tiles of the pass before it that overlap what it
-        // reads -- the same tiles are the last readers of the rows it overwrites, two passes share a buffer set).
-        if (stream_limit > 0 && rc == STSTHIP_OK) {
-            struct Tile {
-                std::uint64_t begin, end;
-                hipEvent_t done;
-                hipStream_t on;
-            };
-            std::vector<hipStream_t> tile_lane(1, s), extra;
-            if (side_streams_for(s, 1, extra))
-                tile_lane.push_back(extra[0]);
-            {
-                // (the scratch planes were allocated for work on `s`)
-                hipEvent_t begin = new_event();
-                ordered(hipEventRecord(begin, s), "hipEventRecord");
-                for (std::size_t v = 1; v < tile_lane.size(); v++)
-                    ordered(hipStreamWaitEvent(tile_lane[v], begin, 0), "hipStreamWaitEvent");
-            }
-            std::vector<std::vector<Tile>> tiles(stream_limit);
-            std::vector<std::uint64_t> frontier(stream_limit, 0);
-            // How deep a column goes: as deep as it takes to keep the chip busy until the next block is there -- and a
-            // little busier: a tile of one block's rows cannot fill the chip on its own (a 2048 x 16384 tile of the
-            // Jacobi example runs at 57 % of the whole grid's rate), two columns side by side do better, so the aim is ONE
-            // or two earlier columns still running when a block arrives.  None: the chip has idled, and the column
-            // before is timed against the blocks' arrival; three or more: the chip is behind, the next column goes
-            // less deep (passes that are begun are completed by the last column whatever the later columns did).
-            std::uint64_t row_bytes_all_planes = 0;
-            for (unsigned p = 0; p < n_planes; p++)
-                row_bytes_all_planes += dom->pitch * desc->plane_elem_size[p];
-            std::uint64_t deep_now = std::min<std::uint64_t>(stream_limit, 16);
-            deep_now = std::max<std::uint64_t>(deep_now - deep_now % quantum, quantum);
-            std::uint64_t deepest = 0;
-            std::vector<hipEvent_t> clocks; // timing events of the columns: begin, end
-            g_launch_concurrency = 2;
-            const bool narrate = std::getenv("STSTHIP_TRACE_STREAM") != nullptr; // (a debugging aid: host times to stderr)
-            auto host_ms = [&] {
-                return std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - started).count();
-            };
-            for (std::size_t k = 0; k < arrival.size() && rc == STSTHIP_OK; k++) {
-                const double waiting_since = host_ms();
-                ordered(hipEventSynchronize(static_cast<hipEvent_t>(arrival[k].ready)), "hipEventSynchronize");
-                if (rc != STSTHIP_OK)
-                    break;
-                const bool last = k + 1 == arrival.size();
-                int behind = 0; // earlier columns that are still running
-                for (std::size_t j = 0; j < k; j++)
-                    behind += event_done(clocks[2 * j + 1]) ? 0 : 1;
-                if (narrate)
-                    std::fprintf(stderr, "[ststhip] block %zu: host waited from %.2f to %.2f ms of the call, %d columns running", k,
-                                 waiting_since, host_ms(), behind);
-                if (k > 0 && !last) {
-                    std::uint64_t want = deep_now;
-                    if (behind == 0) {
-                        // t = what a tile of the column before took (alone, or beside the one before it: the estimate
-                        // is then on the careful side); two columns side by side finish a tile every 0.8 t
-                        // (a block's time over PCIe by its bytes at 55 GB/s: the gaps between the arrival events are no
-                        // measure -- the first blocks of an upload have been seen to arrive 5-6 ms ahead of the rest)
-                        float column_ms = 0.0f;
-                        const double block_ms = double(std::min(arrival[k].row_end, H) - std::min(arrival[k - 1].row_end, H)) *
-                                                double(row_bytes_all_planes) / 55e6;
-                        double grow = 1.25;
-                        if (hipEventElapsedTime(&column_ms, clocks[2 * (k - 1)], clocks[2 * (k - 1) + 1]) == hipSuccess &&
-                            column_ms > 0.0f)
-                            grow = std::min(4.0, std::max(1.25, block_ms / (0.8 * double(column_ms))));
-                        if (narrate)
-                            std::fprintf(stderr, " (column before: %.2f ms, block: %.2f ms)", column_ms, block_ms);
-                        want = std::uint64_t(double(deep_now) * grow + 0.5);
-                    } else if (behind >= 3) {
-                        want = deep_now * 3 / 4;
-                    }
-                    want -= want % quantum;
-                    deep_now = std::min(std::max<std::uint64_t>(want, quantum), stream_limit);
-                }
-                deepest = std::max(deepest, deep_now);
-                const std::uint64_t arrived = last ? H : std::min(arrival[k].row_end, H);
-                hipStream_t on = tile_lane[k % tile_lane.size()];
-                hipEvent_t c0 = nullptr, c1 = nullptr;
-                ordered(hipEventCreate(&c0), "hipEventCreate");
-                ordered(hipEventCreate(&c1), "hipEventCreate");
-                clocks.push_back(c0);
-                clocks.push_back(c1);
-                if (rc != STSTHIP_OK)
-                    break;
-                ordered(hipEventRecord(c0, on), "hipEventRecord");
-                // (the last column completes every pass that was begun)
-                for (std::uint64_t p = 0; p < (last ? deepest : deep_now) && rc == STSTHIP_OK; p++) {
-                    const std::uint64_t above = p == 0 ? arrived : frontier[p - 1];
-                    const std::uint64_t upto = above >= H ? H : (above > tile_g ? above - tile_g : 0);
-                    if (upto <= frontier[p])
-                        break;
-                    const std::uint64_t from_row = frontier[p];
-                    if (p > 0)
-                        for (Tile const &t : tiles[p - 1])
-                            if (t.on != on && t.end + tile_g > from_row && t.begin < upto + tile_g)
-                                ordered(hipStreamWaitEvent(on, t.done, 0), "hipStreamWaitEvent");
-                    g_target_holds_constants = p >= 2 ? 1 : 0;
-                    rc = sweep(ctx, dom, p == 0 ? src : const_cast<const void *const *>(target_of(p - 1)), target_of(p),
-                               from_row, upto, iteration_offset + p * tile_depth, tile_depth, on);
-                    n_launches++;
-                    Tile t{from_row, upto, new_event(), on};
-                    ordered(hipEventRecord(t.done, on), "hipEventRecord");
-                    tiles[p].push_back(t);
-                    frontier[p] = upto;
-                }
-                ordered(hipEventRecord(c1, on), "hipEventRecord");
-                if (narrate)
-                    std::fprintf(stderr, ", column of %llu passes queued by %.2f ms\n",
-                                 (unsigned long long)(last ? deepest : deep_now), host_ms());
-                if (last)
-                    streamed = deepest;
-            }
-            for (std::size_t v = 1; v < tile_lane.size(); v++) {
-                hipEvent_t done = new_event();
-                ordered(hipEventRecord(done, tile_lane[v]), "hipEventRecord");
-                ordered(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent");
-            }
-            if (narrate && rc == STSTHIP_OK && hipStreamSynchronize(s) == hipSuccess) {
-                for (std::size_t k = 0; 2 * k + 1 < clocks.size(); k++) {
-                    float ms = 0.0f, since = 0.0f;
-                    (void)hipEventElapsedTime(&ms, clocks[2 * k], clocks[2 * k + 1]);
-                    (void)hipEventElapsedTime(&since, clocks[0], clocks[2 * k]);
-                    std::fprintf(stderr, "[ststhip] column %zu ran from %.2f for %.2f ms\n", k, since, ms);
-                }
-                std::fprintf(stderr, "[ststhip] streamed passes done at %.2f ms of the call\n", host_ms());
-            }
-            for (hipEvent_t ev : clocks)
-                if (ev)
-                    (void)hipEventDestroy(ev);
-            g_launch_concurrency = 1;
-            g_target_holds_constants = 0;
-            // every pass that was begun is complete now (the last block's column took each of them to the last row)
-            for (std::uint64_t p = 0; p < streamed && rc == STSTHIP_OK; p++)
-                if (frontier[p] != H)
-                    rc = fail(STSTHIP_ERR_INVALID, "internal: a streamed pass is incomplete");
-            if (rc == STSTHIP_OK && streamed > 0) {
-                if (!plan(n_iterations - streamed * tile_depth))
-                    rc = fail(STSTHIP_ERR_INVALID,
-                              "internal: the depth plan does not sum to the generations asked for");
-                // (a probing call's plans differ in length by whole pairs of passes)
-                else if ((streamed + depths.size()) % 2 != total_passes % 2)
-                    rc = fail(STSTHIP_ERR_INVALID, "internal: the plan behind the streamed passes has another parity");
-                strips = suggest_row_strips(H, dom->global_width, desc->strip_width, g_max, depths.size());
-            }
+        // ---- passes behind a source that is still arriving: as row tiles, at the depth the plan starts with ----
+        if (stream_limit > 0 && rc == STSTHIP_OK)
+            streamed = passes_behind_source(c, arrival);
+        if (rc == STSTHIP_OK && streamed > 0) {
+            if (!plan(n_iterations - streamed * tile_depth))
+                rc = fail(STSTHIP_ERR_INVALID,
+                          "internal: the depth plan does not sum to the generations asked for");
+            // (a probing call's plans differ in length by whole pairs of passes)
+            else if ((streamed + depths.size()) % 2 != total_passes % 2)
+                rc = fail(STSTHIP_ERR_INVALID, "internal: the plan behind the streamed passes has another parity");
+            strips = suggest_row_strips(H, dom->global_width, desc->strip_width, g_max, depths.size());
         }
 
         // streams of the strips: strip 0 runs on the caller's stream
-        std::vector<hipStream_t> lane(strips, s);
+        std::vector<hipStream_t> &lane = c.lane, &band_lane = c.band_lane;
+        lane.assign(strips, s);
         if (strips > 1 && rc == STSTHIP_OK) {
             std::vector<hipStream_t> extra;
             if (side_streams_for(s, strips - 1, extra)) {
-                hipEvent_t begin = new_event();
-                ordered(hipEventRecord(begin, s), "hipEventRecord");
+                hipEvent_t begin = kit.record(s);
                 for (int v = 1; v < strips; v++) {
                     lane[v] = extra[v - 1];
-                    ordered(hipStreamWaitEvent(lane[v], begin, 0), "hipStreamWaitEvent");
+                    kit.wait(lane[v], begin);
                 }
             } else {
                 strips = 1;
                 lane.assign(1, s);
             }
         }
-        std::vector<std::uint64_t> bound(strips + 1);
+        std::vector<std::uint64_t> &bound = c.bound;
+        bound.resize(strips + 1);
         for (int v = 0; v <= strips; v++)
             bound[v] = H * std::uint64_t(v) / std::uint64_t(strips);
         // unequal strips drift out of phase, so one strip's tail meets the other's bulk (400 while the bands sat in
@@ -1664,14 +1803,13 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
         //   interior(v, p) after bands(v-1 .. v+1, p-1)                               [own interior(p-1): stream order]
         // -- every row a launch reads was written by one of those, and every row it overwrites (the other buffer
         // set) was last read by one of those.
-        std::vector<hipStream_t> band_lane(strips, nullptr);
-        const bool bands_beside = strips > 1 && opt().bands_beside_interior != 0 &&
-                                  band_streams_for(s, strips, band_lane);
+        band_lane.assign(strips, nullptr);
+        const bool bands_beside = c.bands_beside = strips > 1 && opt().bands_beside_interior != 0 &&
+                                                   band_streams_for(s, strips, band_lane);
         if (bands_beside) {
-            hipEvent_t begin = new_event();
-            ordered(hipEventRecord(begin, s), "hipEventRecord");
+            hipEvent_t begin = kit.record(s);
             for (int v = 0; v < strips; v++)
-                ordered(hipStreamWaitEvent(band_lane[v], begin, 0), "hipStreamWaitEvent");
+                kit.wait(band_lane[v], begin);
         }
         // Strips with moving boundaries instead of strips with boundary bands (see the pass loop).  The boundaries move
         // around their places of rest: by what the call's plan moves them, at most a quarter of a strip's rows.
@@ -1681,35 +1819,32 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
         skew_span = std::min<std::uint64_t>(skew_span, std::min<std::uint64_t>(H / std::uint64_t(2 * strips), 2048 + 2 * g_max));
         const bool skewed_strips = strips >= 2 && !profiling && opt().skewed_strips != 0 &&
                                    H >= std::uint64_t(strips) * 32 * g_max && skew_span >= 2 * g_max;
-        std::uint64_t skew_offset = 0, skew_g_before = 0; // how far below their highest places the boundaries are
+        MovingBoundary skew;
+        skew.span = skew_span;
         std::vector<hipEvent_t> skew_done(strips, nullptr); // per strip: its launch of the previous pass
-        std::vector<hipEvent_t> bands_done(strips, nullptr);    // per strip: bands of the previous pass
-        std::vector<hipEvent_t> interior_done(strips, nullptr); // per strip: interior of the previous pass
-        g_launch_concurrency = strips;
+        c.bands_done.assign(strips, nullptr);
+        c.interior_done.assign(strips, nullptr);
+        g_launch.concurrency = strips;
 
         // the last pass must land in dst; the input is never written
-        const void *const *from = streamed ? const_cast<const void *const *>(target_of(streamed - 1)) : src;
+        const void *const *from = streamed ? const_cast<const void *const *>(c.target_of(streamed - 1)) : src;
         std::uint64_t iteration = iteration_offset + streamed * tile_depth;
         // a point in time on every stream of the call: everything queued so far has finished before `ev`, nothing
         // queued later starts before it (the boundaries of the depth probes' timed groups)
         auto fence_all = [&](hipEvent_t ev) {
+            kit.join(s, lane.data() + 1, lane.data() + strips);
+            if (bands_beside)
+                kit.join(s, band_lane.data(), band_lane.data() + strips);
+            kit.ordered(hipEventRecord(ev, s), "hipEventRecord");
             for (int v = 1; v < strips; v++)
-                ordered(hipStreamWaitEvent(s, [&] { hipEvent_t e = new_event(); ordered(hipEventRecord(e, lane[v]), "hipEventRecord"); return e; }(), 0),
-                        "hipStreamWaitEvent");
+                kit.wait(lane[v], ev);
             if (bands_beside)
                 for (int v = 0; v < strips; v++)
-                    ordered(hipStreamWaitEvent(s, [&] { hipEvent_t e = new_event(); ordered(hipEventRecord(e, band_lane[v]), "hipEventRecord"); return e; }(), 0),
-                            "hipStreamWaitEvent");
-            ordered(hipEventRecord(ev, s), "hipEventRecord");
-            for (int v = 1; v < strips; v++)
-                ordered(hipStreamWaitEvent(lane[v], ev, 0), "hipStreamWaitEvent");
-            if (bands_beside)
-                for (int v = 0; v < strips; v++)
-                    ordered(hipStreamWaitEvent(band_lane[v], ev, 0), "hipStreamWaitEvent");
+                    kit.wait(band_lane[v], ev);
         };
         if (probing)
             for (hipEvent_t &ev : probe_events)
-                ordered(hipEventCreate(&ev), "hipEventCreate");
+                kit.ordered(hipEventCreate(&ev), "hipEventCreate");
         for (std::size_t pass = 0; pass < depths.size() && rc == STSTHIP_OK; pass++) {
             if (probing && (pass == 1 || pass == 3 || pass == probe_passes)) {
                 const int boundary = pass == 1 ? 0 : (pass == 3 ? 1 : 2);
@@ -1717,9 +1852,9 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
                 if (boundary == 2) {
                     // the host waits for the probes here (a few milliseconds, once per kernel family and grid shape)
                     float ms_deep = 0.0f, ms_alt = 0.0f;
-                    ordered(hipEventSynchronize(probe_events[2]), "hipEventSynchronize");
-                    ordered(hipEventElapsedTime(&ms_deep, probe_events[0], probe_events[1]), "hipEventElapsedTime");
-                    ordered(hipEventElapsedTime(&ms_alt, probe_events[1], probe_events[2]), "hipEventElapsedTime");
+                    kit.ordered(hipEventSynchronize(probe_events[2]), "hipEventSynchronize");
+                    kit.ordered(hipEventElapsedTime(&ms_deep, probe_events[0], probe_events[1]), "hipEventElapsedTime");
+                    kit.ordered(hipEventElapsedTime(&ms_alt, probe_events[1], probe_events[2]), "hipEventElapsedTime");
                     if (rc != STSTHIP_OK)
                         break;
                     // (the shallower depth has to win by 2 %: a tie keeps the plan that is already laid out)
@@ -1735,18 +1870,17 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
                     tuned_depths()[TunedKey{desc->tune_key, H, dom->global_width}] = take_alt ? alt : deep;
                 }
             }
-            void *const *to = target_of(streamed + pass);
+            void *const *to = c.target_of(streamed + pass);
             // targets alternate, and every pass writes all rows: from the third pass on the target already holds
             // what the pass before the previous one stored there, in particular the fields that never change
-            g_target_holds_constants = streamed + pass >= 2 ? 1 : 0;
+            g_launch.target_holds_constants = streamed + pass >= 2 ? 1 : 0;
             const std::uint64_t g = std::uint64_t(depths[pass]) * desc->halo_depth_per_generation;
             hipEvent_t t0 = nullptr, t1 = nullptr;
             if (profiling) {
-                ordered(hipEventCreate(&t0), "hipEventCreate");
-                ordered(hipEventCreate(&t1), "hipEventCreate");
-                ordered(hipEventRecord(t0, s), "hipEventRecord");
+                kit.ordered(hipEventCreate(&t0), "hipEventCreate");
+                kit.ordered(hipEventCreate(&t1), "hipEventCreate");
+                kit.ordered(hipEventRecord(t0, s), "hipEventRecord");
             }
-            std::vector<hipEvent_t> bands_now(strips, nullptr), interior_now(strips, nullptr);
             if (skewed_strips) {
                 // Strips whose common boundaries move UP by a launch's ghost rows from pass to pass (the larger of this
                 // pass's and the one's before): a strip of pass p then reads nothing the strip BELOW it wrote in pass
@@ -1754,107 +1888,34 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
                 // for its own, nothing else; the uppermost strip's launches are a chain of their own.  No boundary
                 // bands, one launch per strip and pass.  When the boundaries have moved a span, every strip waits for
                 // the one below it once and the boundaries start over.
-                const std::uint64_t shift = std::max(g, skew_g_before);
-                bool restart = false;
-                if (skew_offset + shift > skew_span) {
-                    skew_offset = 0;
-                    restart = true;
-                } else {
-                    skew_offset += shift;
-                }
-                skew_g_before = g;
+                const bool restart = skew.step(g);
                 std::vector<hipEvent_t> done_now(strips, nullptr);
                 for (int v = 0; v < strips && rc == STSTHIP_OK; v++) {
-                    const std::uint64_t top = v == 0 ? 0 : bound[v] + skew_span / 2 - skew_offset;
-                    const std::uint64_t end = v + 1 == strips ? H : bound[v + 1] + skew_span / 2 - skew_offset;
-                    if (v > 0 && skew_done[v - 1])
-                        ordered(hipStreamWaitEvent(lane[v], skew_done[v - 1], 0), "hipStreamWaitEvent");
-                    if (restart && v + 1 < strips && skew_done[v + 1])
-                        ordered(hipStreamWaitEvent(lane[v], skew_done[v + 1], 0), "hipStreamWaitEvent");
+                    const std::uint64_t top = v == 0 ? 0 : bound[v] + skew.span / 2 - skew.offset;
+                    const std::uint64_t end = v + 1 == strips ? H : bound[v + 1] + skew.span / 2 - skew.offset;
+                    if (v > 0)
+                        kit.wait(lane[v], skew_done[v - 1]);
+                    if (restart && v + 1 < strips)
+                        kit.wait(lane[v], skew_done[v + 1]);
                     rc = sweep(ctx, dom, from, to, top, end, iteration, depths[pass], lane[v]);
-                    n_launches++;
-                    done_now[v] = new_event();
-                    ordered(hipEventRecord(done_now[v], lane[v]), "hipEventRecord");
+                    c.n_launches++;
+                    done_now[v] = kit.record(lane[v]);
                 }
                 skew_done.swap(done_now);
-                if (profiling) {
-                    ordered(hipEventRecord(t1, s), "hipEventRecord");
-                    timed.emplace_back(t0, t1);
-                }
-                from = const_cast<const void *const *>(to);
-                iteration += depths[pass];
-                continue;
+            } else {
+                band_pass(c, from, to, iteration, depths[pass], g);
             }
-            for (int v = 0; v < strips && rc == STSTHIP_OK; v++) {
-                const std::uint64_t a = bound[v], b = bound[v + 1];
-                if (strips == 1) {
-                    rc = sweep(ctx, dom, from, to, a, b, iteration, depths[pass], lane[v]);
-                    n_launches++;
-                    continue;
-                }
-                hipStream_t bands_on = bands_beside ? band_lane[v] : lane[v];
-                // bands read the neighbours' bands of the previous pass (and will overwrite rows
-                // the neighbours' previous bands read): wait for them
-                if (v > 0 && bands_done[v - 1])
-                    ordered(hipStreamWaitEvent(bands_on, bands_done[v - 1], 0), "hipStreamWaitEvent");
-                if (v + 1 < strips && bands_done[v + 1])
-                    ordered(hipStreamWaitEvent(bands_on, bands_done[v + 1], 0), "hipStreamWaitEvent");
-                if (bands_beside && interior_done[v])
-                    ordered(hipStreamWaitEvent(bands_on, interior_done[v], 0), "hipStreamWaitEvent");
-                const std::uint64_t top_end = (v > 0) ? std::min(a + g, b) : a;
-                const std::uint64_t bot_begin = (v + 1 < strips) ? std::max(b - std::min(g, b - a), top_end) : b;
-                if (top_end > a) {
-                    rc = sweep(ctx, dom, from, to, a, top_end, iteration, depths[pass], bands_on);
-                    n_launches++;
-                }
-                if (rc == STSTHIP_OK && bot_begin < b) {
-                    rc = sweep(ctx, dom, from, to, bot_begin, b, iteration, depths[pass], bands_on);
-                    n_launches++;
-                }
-                bands_now[v] = new_event();
-                ordered(hipEventRecord(bands_now[v], bands_on), "hipEventRecord");
-                if (bands_beside) {
-                    // the interior reads this strip's previous bands, and -- when this pass is shallower than the
-                    // previous one -- overwrites rows next to them that the neighbours' previous bands read
-                    for (int w = std::max(v - 1, 0); w <= std::min(v + 1, strips - 1); w++)
-                        if (bands_done[w])
-                            ordered(hipStreamWaitEvent(lane[v], bands_done[w], 0), "hipStreamWaitEvent");
-                }
-                if (rc == STSTHIP_OK && top_end < bot_begin) {
-                    rc = sweep(ctx, dom, from, to, top_end, bot_begin, iteration, depths[pass], lane[v]);
-                    n_launches++;
-                }
-                if (bands_beside) {
-                    interior_now[v] = new_event();
-                    ordered(hipEventRecord(interior_now[v], lane[v]), "hipEventRecord");
-                }
-            }
-            bands_done.swap(bands_now);
-            interior_done.swap(interior_now);
             if (profiling) {
-                ordered(hipEventRecord(t1, s), "hipEventRecord");
+                kit.ordered(hipEventRecord(t1, s), "hipEventRecord");
                 timed.emplace_back(t0, t1);
             }
             from = const_cast<const void *const *>(to);
             iteration += depths[pass];
         }
-        // the band streams join the caller's stream too
+        // join: the caller's stream continues after every band stream and every strip has finished
         if (bands_beside)
-            for (int v = 0; v < strips; v++) {
-                hipEvent_t done = new_event();
-                ordered(hipEventRecord(done, band_lane[v]), "hipEventRecord");
-                ordered(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent");
-            }
-        g_launch_concurrency = 1;
-        g_target_holds_constants = 0;
-        g_tdv_table = nullptr;
-        g_tdv_count = 0;
-        // join: the caller's stream continues after every strip has finished
-        for (int v = 1; v < strips; v++) {
-            hipEvent_t done = new_event();
-            ordered(hipEventRecord(done, lane[v]), "hipEventRecord");
-            ordered(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent");
-        }
+            kit.join(s, band_lane.data(), band_lane.data() + strips);
+        kit.join(s, lane.data() + 1, lane.data() + strips);
     }
     if (streamed > 0 && std::getenv("STSTHIP_TRACE_STREAM")) {
         const double queued = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - started).count();
@@ -1863,18 +1924,14 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
                      (unsigned long long)streamed, queued,
                      std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - started).count());
     }
-    if (rc == STSTHIP_OK && (blocking || profiling)) {
-        hipError_t err = hipStreamSynchronize(s);
-        if (err != hipSuccess)
-            rc = hip_fail(err, "hipStreamSynchronize");
-    }
+    if (rc == STSTHIP_OK && (blocking || profiling))
+        kit.ordered(hipStreamSynchronize(s), "hipStreamSynchronize");
     // released on the caller's stream, which every strip has been joined into above: the blocks go to
     // another stream (or the host) only after the event recorded here -- also when a launch failed midway
     for (unsigned p = 0; p < n_planes; p++)
-        if (scratch[p])
-            ststhip_free_async(scratch[p], s);
-    if (tdv_table)
-        ststhip_free_async(tdv_table, s);
+        if (c.scratch[p])
+            ststhip_free_async(c.scratch[p], s);
+    values.close(s);
     for (hipEvent_t ev : probe_events)
         if (ev)
             (void)hipEventDestroy(ev);
@@ -1890,7 +1947,7 @@ int ststhip_run_passes(ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_de
         std::chrono::duration<double> elapsed = std::chrono::high_resolution_clock::now() - started;
         info->walltime_s = elapsed.count();
         info->kernel_time_s = kernel_s;
-        info->n_launches = n_launches;
+        info->n_launches = c.n_launches;
         info->n_processed_cells = n_iterations * dom->global_height * dom->global_width;
         info->n_streamed_passes = streamed;
     }
@@ -2273,10 +2330,9 @@ void strip_bounds(std::uint64_t total, int n, int r, std::uint64_t &a, std::uint
     b = a + base + (std::uint64_t(r) < extra ? 1 : 0);
 }
 
-// ghost rows of depth g next to the owned rows of buffer set `set`, on the comm stream
-int strip_exchange(Strip &st, int set, std::uint64_t g) {
-    if (st.n_ranks == 1 || g == 0)
-        return STSTHIP_OK;
+// ghost rows of depth g next to the owned rows of buffer set `set`, on the comm stream: whole buffer rows (a block's
+// ghost columns included)
+int exchange_rows(Strip &st, int set, std::uint64_t g) {
     const void *send_up[16], *send_down[16];
     void *recv_up[16], *recv_down[16];
     std::size_t row_bytes[16];
@@ -2289,12 +2345,17 @@ int strip_exchange(Strip &st, int set, std::uint64_t g) {
         send_down[p] = base + (o_stop - g) * row_bytes[p];
         recv_down[p] = base + o_stop * row_bytes[p];
     }
-    st.n_exchanges++;
     if (st.comm)
         return ststhip_comm_exchange_rows(st.comm, int(st.n_planes), send_up, send_down, recv_up, recv_down, row_bytes,
                                           std::size_t(g), st.comm_stream);
     return st.exchange(st.exchange_ctx, int(st.n_planes), send_up, send_down, recv_up, recv_down, row_bytes,
                        std::size_t(g), st.comm_stream);
+}
+int strip_exchange(Strip &st, int set, std::uint64_t g) {
+    if (st.n_ranks == 1 || g == 0)
+        return STSTHIP_OK;
+    st.n_exchanges++;
+    return exchange_rows(st, set, g);
 }
 // the 2-D block driver (below)
 extern "C++" {
@@ -2304,72 +2365,132 @@ int block_advance(Strip *st, std::uint64_t iteration_offset, std::uint64_t n_gen
 } // namespace
 
 namespace {
-// the part of strip creation that does not depend on where the sweep comes from: geometry, streams, buffers
-int finish_strip(Strip *st, const ststhip_domain *dom, ststhip_strip *strip) {
+// ---- creation, shared by strips and blocks
+// the whole grid, as resolve_app and the sweeps of a strip see it (a block also names its columns: `block`)
+ststhip_domain whole_grid(std::uint64_t rows, std::uint64_t cols, bool block = false) {
+    ststhip_domain whole = {};
+    whole.global_height = rows;
+    whole.global_width = cols;
+    whole.pitch = cols;
+    whole.row_origin = 0;
+    whole.local_rows = rows;
+    whole.local_cols = block ? cols : 0;
+    return whole;
+}
+
+// where a strip lies in the chain and whom it talks to
+void place_strip(Strip *st, std::uint64_t total_rows, std::uint64_t width, int rank, int n_ranks, ststhip_comm comm,
+                 ststhip_exchange_fn exchange, void *exchange_ctx) {
+    st->rank = rank;
+    st->n_ranks = n_ranks;
+    st->comm = static_cast<Comm *>(comm);
+    st->exchange = exchange;
+    st->exchange_ctx = exchange_ctx;
+    st->total_rows = total_rows;
+    st->width = width;
+    strip_bounds(total_rows, n_ranks, rank, st->row_begin, st->row_end);
+}
+
+// a registered transition function: the strip keeps its arguments, the sweep is the form resolve_app chooses
+int use_app_sweep(Strip *st, const AppEntry *e, const char *app, const void *tf_params, const void *halo_cell,
+                  const ststhip_domain *&dom) {
+    st->app = app;
+    st->params.assign(static_cast<const unsigned char *>(tf_params),
+                      static_cast<const unsigned char *>(tf_params) + std::max<std::uint32_t>(e->info.params_size, 1));
+    st->halo.assign(static_cast<const unsigned char *>(halo_cell), static_cast<const unsigned char *>(halo_cell) + e->info.cell_size);
+    return resolve_app(st->resolved, st->app.c_str(), st->params.data(), st->halo.data(), dom, nullptr, nullptr, false);
+}
+
+// the caller's sweep: no registry entry, no run window to maintain
+void use_custom_sweep(Strip *st, ststhip_sweep_fn sweep, void *ctx, const ststhip_sweep_desc *desc) {
+    st->resolved.entry = nullptr;
+    st->resolved.trampoline = sweep;
+    st->resolved.ctx = ctx;
+    st->resolved.desc = *desc;
+}
+
+// Checks the sweep's description and fixes the ghost depth: g_max, launches per ghost exchange (STSTHIP_EXCHANGE_EVERY,
+// else `default_every`) and the ghost cells the buffers hold on every side with a neighbour.  `thinnest`: the fewest
+// rows (a block: rows or columns) a rank owns.
+int plan_ghosts(Strip *st, std::uint64_t thinnest, int default_every, const char *too_thin) {
     const ststhip_sweep_desc &d = st->resolved.desc;
-    if (d.n_planes == 0 || d.n_planes > 16 || d.max_generations == 0) {
-        delete st;
+    if (d.n_planes == 0 || d.n_planes > 16 || d.max_generations == 0)
         return fail(STSTHIP_ERR_INVALID, "bad sweep description");
-    }
     st->n_planes = d.n_planes;
-    // (the deepest launch the strip driver plans: the family's trusted depth, ststhip_strip_advance)
+    // (the deepest launch the drivers plan: the family's trusted depth, ststhip_strip_advance)
     st->g_max = std::uint64_t(d.alt_generations && d.alt_generations < d.max_generations ? d.alt_generations : d.max_generations) *
                 d.halo_depth_per_generation;
+    st->exchange_every = 1;
+    if (st->n_ranks > 1) {
+        int every = opt().exchange_every > 0 ? std::min(opt().exchange_every, 16) : default_every;
+        while (every > 1 && thinnest < 4 * st->g_max * std::uint64_t(every))
+            every--;
+        st->exchange_every = every;
+    }
+    st->ghost = st->g_max * std::uint64_t(st->exchange_every);
+    if (st->n_ranks > 1 && thinnest < 2 * st->ghost)
+        return fail(STSTHIP_ERR_INVALID, too_thin);
+    return STSTHIP_OK;
+}
+
+// the two streams and the two buffer sets (st->dom is complete), cleared
+int create_streams_and_buffers(Strip *st, bool comm_stream_priority, const char *what) {
+    int rc = STSTHIP_OK;
+    hipError_t err = hipStreamCreateWithFlags(&st->compute, hipStreamNonBlocking);
+    if (err == hipSuccess)
+        err = comm_stream_priority ? create_band_stream(&st->comm_stream)
+                                   : hipStreamCreateWithFlags(&st->comm_stream, hipStreamNonBlocking);
+    for (int set = 0; set < 2 && err == hipSuccess && rc == STSTHIP_OK; set++)
+        for (unsigned p = 0; p < st->n_planes && rc == STSTHIP_OK; p++) {
+            st->elem[p] = st->resolved.desc.plane_elem_size[p];
+            const std::size_t bytes = std::size_t(st->local_rows) * st->dom.pitch * st->elem[p];
+            rc = ststhip_malloc_async(&st->planes[set][p], bytes, st->compute);
+            if (rc == STSTHIP_OK)
+                err = hipMemsetAsync(st->planes[set][p], 0, bytes, st->compute);
+        }
+    return err != hipSuccess ? hip_fail(err, what) : rc;
+}
+
+// waits for the set-up queued on the compute stream and hands the strip out, or destroys it
+int hand_out(Strip *st, int rc, const char *what, ststhip_strip *out) {
+    hipError_t err;
+    if (rc == STSTHIP_OK && (err = hipStreamSynchronize(st->compute)) != hipSuccess)
+        rc = hip_fail(err, what);
+    if (rc != STSTHIP_OK) {
+        ststhip_strip_destroy(st);
+        return rc;
+    }
+    *out = st;
+    return STSTHIP_OK;
+}
+
+// the part of strip creation that does not depend on where the sweep comes from: geometry, streams, buffers; owns `st`
+int finish_strip(Strip *st, const ststhip_domain *dom, ststhip_strip *strip) {
     std::uint64_t thinnest = st->total_rows;
     for (int r = 0; r < st->n_ranks; r++) {
         std::uint64_t a, b;
         strip_bounds(st->total_rows, st->n_ranks, r, a, b);
         thinnest = std::min(thinnest, b - a);
     }
-    // launches per ghost exchange (STSTHIP_EXCHANGE_EVERY, else by the strips' height): a thin strip's launch is as
-    // short as the band -> exchange chain in front of the next one, so it groups four launches per exchange, a thick
-    // one two (one MI355X, the compute side of a rank, profiles/r03_thin_strips.txt: 2048 rows 3910 / 4010 / 4090
-    // Gcell/s per GPU at 1 / 2 / 4 launches per exchange)
-    st->exchange_every = 1;
-    if (st->n_ranks > 1) {
-        int every = opt().exchange_every > 0 ? std::min(opt().exchange_every, 16) : (thinnest <= 4096 ? 4 : 2);
-        while (every > 1 && thinnest < 4 * st->g_max * std::uint64_t(every))
-            every--;
-        st->exchange_every = every;
-    }
-    st->ghost = st->g_max * std::uint64_t(st->exchange_every);
-    if (st->n_ranks > 1 && thinnest < 2 * st->ghost) {
+    // launches per ghost exchange by the strips' height: a thin strip's launch is as short as the band -> exchange
+    // chain in front of the next one, so it groups four launches per exchange, a thick one two (one MI355X, the compute
+    // side of a rank, profiles/r03_thin_strips.txt: 2048 rows 3910 / 4010 / 4090 Gcell/s per GPU at 1 / 2 / 4 launches
+    // per exchange)
+    if (int rc = plan_ghosts(st, thinnest, thinnest <= 4096 ? 4 : 2,
+                             "strips are thinner than two ghost depths: use fewer ranks, a larger grid or a "
+                             "smaller STSTHIP_EXCHANGE_EVERY")) {
         delete st;
-        return fail(STSTHIP_ERR_INVALID, "strips are thinner than two ghost depths: use fewer ranks, a larger grid or a "
-                                         "smaller STSTHIP_EXCHANGE_EVERY");
+        return rc;
     }
     st->row_origin = std::int64_t(st->row_begin) - std::int64_t(st->ghost);
     st->local_rows = (st->row_end - st->row_begin) + 2 * st->ghost;
     st->dom = *dom; // width and pitch possibly in words
     st->dom.row_origin = st->row_origin;
     st->dom.local_rows = st->local_rows;
-    int rc = STSTHIP_OK;
-    hipError_t err = hipStreamCreateWithFlags(&st->compute, hipStreamNonBlocking);
     // the exchange stream has normal priority: as a third highest-priority stream beside the band streams of two
     // sub-strips it cost 8-30 % (streams of one priority share few hardware queues, and a band waiting for its events
     // holds up whatever sits behind it in the same queue: profiles/r02_thin_strips.txt section 7)
-    if (err == hipSuccess)
-        err = opt().comm_stream_priority
-                  ? create_band_stream(&st->comm_stream)
-                  : hipStreamCreateWithFlags(&st->comm_stream, hipStreamNonBlocking);
-    for (int set = 0; set < 2 && err == hipSuccess && rc == STSTHIP_OK; set++)
-        for (unsigned p = 0; p < st->n_planes && rc == STSTHIP_OK; p++) {
-            st->elem[p] = d.plane_elem_size[p];
-            const std::size_t bytes = std::size_t(st->local_rows) * st->dom.pitch * st->elem[p];
-            rc = ststhip_malloc_async(&st->planes[set][p], bytes, st->compute);
-            if (rc == STSTHIP_OK)
-                err = hipMemsetAsync(st->planes[set][p], 0, bytes, st->compute);
-        }
-    if (err != hipSuccess)
-        rc = hip_fail(err, "strip set-up");
-    if (rc == STSTHIP_OK && (err = hipStreamSynchronize(st->compute)) != hipSuccess)
-        rc = hip_fail(err, "strip set-up");
-    if (rc != STSTHIP_OK) {
-        ststhip_strip_destroy(st);
-        return rc;
-    }
-    *strip = st;
-    return STSTHIP_OK;
+    return hand_out(st, create_streams_and_buffers(st, opt().comm_stream_priority != 0, "strip set-up"), "strip set-up", strip);
 }
 } // namespace
 
@@ -2386,28 +2507,10 @@ int ststhip_strip_create(const char *app, const void *tf_params, const void *hal
     if (int rc = ststhip_init(-1))
         return rc;
     Strip *st = new Strip;
-    st->app = app;
-    st->params.assign(static_cast<const unsigned char *>(tf_params),
-                      static_cast<const unsigned char *>(tf_params) + std::max<std::uint32_t>(e->info.params_size, 1));
-    st->halo.assign(static_cast<const unsigned char *>(halo_cell),
-                    static_cast<const unsigned char *>(halo_cell) + e->info.cell_size);
-    st->rank = rank;
-    st->n_ranks = n_ranks;
-    st->comm = static_cast<Comm *>(comm);
-    st->exchange = exchange;
-    st->exchange_ctx = exchange_ctx;
-    st->total_rows = total_rows;
-    st->width = width;
-    strip_bounds(total_rows, n_ranks, rank, st->row_begin, st->row_end);
-    ststhip_domain whole = {};
-    whole.global_height = total_rows;
-    whole.global_width = width;
-    whole.pitch = width;
-    whole.row_origin = 0;
-    whole.local_rows = total_rows;
+    place_strip(st, total_rows, width, rank, n_ranks, comm, exchange, exchange_ctx);
+    const ststhip_domain whole = whole_grid(total_rows, width);
     const ststhip_domain *dom = &whole;
-    int rc = resolve_app(st->resolved, st->app.c_str(), st->params.data(), st->halo.data(), dom, nullptr, nullptr, false);
-    if (rc != STSTHIP_OK) {
+    if (int rc = use_app_sweep(st, e, app, tf_params, halo_cell, dom)) {
         delete st;
         return rc;
     }
@@ -2424,24 +2527,9 @@ int ststhip_strip_create_custom(ststhip_sweep_fn sweep, void *ctx, const ststhip
     if (int rc = ststhip_init(-1))
         return rc;
     Strip *st = new Strip;
-    st->rank = rank;
-    st->n_ranks = n_ranks;
-    st->comm = static_cast<Comm *>(comm);
-    st->exchange = exchange;
-    st->exchange_ctx = exchange_ctx;
-    st->total_rows = total_rows;
-    st->width = width;
-    strip_bounds(total_rows, n_ranks, rank, st->row_begin, st->row_end);
-    st->resolved.entry = nullptr; // the caller's sweep: no registry entry, no run window to maintain
-    st->resolved.trampoline = sweep;
-    st->resolved.ctx = ctx;
-    st->resolved.desc = *desc;
-    ststhip_domain whole = {};
-    whole.global_height = total_rows;
-    whole.global_width = width;
-    whole.pitch = width;
-    whole.row_origin = 0;
-    whole.local_rows = total_rows;
+    place_strip(st, total_rows, width, rank, n_ranks, comm, exchange, exchange_ctx);
+    use_custom_sweep(st, sweep, ctx, desc);
+    const ststhip_domain whole = whole_grid(total_rows, width);
     return finish_strip(st, &whole, strip);
 }
 
@@ -2568,24 +2656,9 @@ int ststhip_strip_advance(ststhip_strip strip, uint64_t iteration_offset, uint64
     const std::uint64_t hpg = d.halo_depth_per_generation;
     const std::uint64_t a = st->row_begin, b = st->row_end;
     const std::size_t m = std::size_t(st->exchange_every);
-    int rc = STSTHIP_OK;
-    EventPool events;
-    auto ordered = [&](hipError_t err, const char *what) {
-        if (err != hipSuccess && rc == STSTHIP_OK)
-            rc = hip_fail(err, what);
-    };
-    auto record = [&](hipStream_t on) {
-        hipEvent_t ev = events.take();
-        if (!ev)
-            ordered(hipErrorUnknown, "hipEventCreateWithFlags");
-        else
-            ordered(hipEventRecord(ev, on), "hipEventRecord");
-        return ev;
-    };
-    auto wait = [&](hipStream_t who, hipEvent_t ev) {
-        if (ev)
-            ordered(hipStreamWaitEvent(who, ev, 0), "hipStreamWaitEvent");
-    };
+    LaunchStateGuard idle_on_return;
+    OrderKit kit;
+    int &rc = kit.rc;
 
     const bool has_up = st->rank > 0, has_down = st->rank + 1 < st->n_ranks;
     hipStream_t lane = st->compute, band = nullptr;
@@ -2622,49 +2695,36 @@ int ststhip_strip_advance(ststhip_strip strip, uint64_t iteration_offset, uint64
             lane_low = st->side;
         }
     }
-    std::uint64_t sub_offset = 0, sub_g_before = 0; // how far below its highest place the boundary is
+    MovingBoundary sub; // (of the two sub-strips)
+    sub.span = sub_span;
     hipEvent_t upper_done = nullptr, lower_done = nullptr;
-    g_launch_concurrency = lane_low ? 2 : 1;
+    g_launch.concurrency = lane_low ? 2 : 1;
 
-    // one device table of time-dependent values for the whole call, as in ststhip_run_passes
-    void *tdv_table = nullptr;
-    if (d.tdv_size > 0 && d.fill_tdv) {
-        const std::size_t bytes = std::size_t(d.tdv_size) * n_generations;
-        rc = ststhip_malloc_async(&tdv_table, bytes, lane);
-        if (rc == STSTHIP_OK) {
-            std::vector<unsigned char> values(bytes);
-            d.fill_tdv(st->resolved.ctx, iteration_offset, n_generations, values.data());
-            ordered(hipMemcpyAsync(tdv_table, values.data(), bytes, hipMemcpyHostToDevice, lane), "hipMemcpyAsync");
-            ordered(hipStreamSynchronize(lane), "hipStreamSynchronize"); // `values` is pageable and goes out of scope
-            g_tdv_table = tdv_table;
-            g_tdv_first = iteration_offset;
-            g_tdv_count = n_generations;
-            g_tdv_size = d.tdv_size;
-        }
-    }
+    ValuesTable values;
+    values.open(d, st->resolved.ctx, iteration_offset, n_generations, lane, kit);
     auto group_depth = [&](std::size_t first) {
         std::uint64_t sum = 0;
         for (std::size_t i = first; i < std::min(first + m, depths.size()); i++)
             sum += depths[i] * hpg;
         return sum;
     };
-    hipEvent_t begin = record(lane); // everything queued so far: a previous advance, uploads, the table
-    wait(st->comm_stream, begin);
+    hipEvent_t begin = kit.record(lane); // everything queued so far: a previous advance, uploads, the table
+    kit.wait(st->comm_stream, begin);
     if (band)
-        wait(band, begin);
+        kit.wait(band, begin);
     if (lane_low)
-        wait(lane_low, begin);
+        kit.wait(lane_low, begin);
     hipEvent_t ghosts_ready = nullptr;
     if (st->n_ranks > 1 && rc == STSTHIP_OK) {
         rc = strip_exchange(*st, st->current, group_depth(0));
-        ghosts_ready = record(st->comm_stream);
+        ghosts_ready = kit.record(st->comm_stream);
     }
     std::uint64_t iteration = iteration_offset;
     for (std::size_t first = 0; first < depths.size() && rc == STSTHIP_OK; first += m) {
         const std::size_t last = std::min(first + m, depths.size()) - 1;
-        wait(lane, ghosts_ready); // the group's first launch reads the ghost rows of this group
+        kit.wait(lane, ghosts_ready); // the group's first launch reads the ghost rows of this group
         if (lane_low)
-            wait(lane_low, ghosts_ready);
+            kit.wait(lane_low, ghosts_ready);
         std::uint64_t widen = group_depth(first); // E_(j-1): how far beyond the owned rows the launch's input is valid
         for (std::size_t i = first; i <= last && rc == STSTHIP_OK; i++) {
             const std::uint32_t depth = depths[i];
@@ -2685,23 +2745,15 @@ int ststhip_strip_advance(ststhip_strip strip, uint64_t iteration_offset, uint64
                     sweep(r0, r1, lane);
                     return;
                 }
-                const std::uint64_t shift = std::max<std::uint64_t>(depth * hpg, sub_g_before);
-                bool restart = false;
-                if (sub_offset + shift > sub_span) {
-                    sub_offset = 0;
-                    restart = true;
-                } else {
-                    sub_offset += shift;
-                }
-                sub_g_before = depth * hpg;
-                const std::uint64_t boundary = std::min(std::max((a + b) / 2 + sub_span / 2 - sub_offset, r0), r1);
+                const bool restart = sub.step(depth * hpg);
+                const std::uint64_t boundary = std::min(std::max((a + b) / 2 + sub.span / 2 - sub.offset, r0), r1);
                 if (restart)
-                    wait(lane, lower_done);
+                    kit.wait(lane, lower_done);
                 sweep(r0, boundary, lane);
-                hipEvent_t upper = record(lane);
-                wait(lane_low, upper_done);
+                hipEvent_t upper = kit.record(lane);
+                kit.wait(lane_low, upper_done);
                 sweep(boundary, r1, lane_low);
-                lower_done = record(lane_low);
+                lower_done = kit.record(lane_low);
                 upper_done = upper;
             };
             const bool feeds_exchange = i == last && last + 1 < depths.size() && (has_up || has_down);
@@ -2709,29 +2761,29 @@ int ststhip_strip_advance(ststhip_strip strip, uint64_t iteration_offset, uint64
                 const std::uint64_t next = group_depth(last + 1);
                 const std::uint64_t top_end = has_up ? a + next : a;
                 const std::uint64_t bot_begin = has_down ? b - next : b;
-                wait(band, record(lane)); // the bands read what the previous launch left (and what `lane` waited for)
+                kit.wait(band, kit.record(lane)); // the bands read what the previous launch left (and what `lane` waited for)
                 if (lane_low)
-                    wait(band, record(lane_low));
+                    kit.wait(band, kit.record(lane_low));
                 if (has_up && has_down && top_end < bot_begin) {
                     // both bands as one launch with a hole where the interior is: one band latency in front of the exchange
-                    g_row_hole_begin = top_end;
-                    g_row_hole_end = bot_begin;
+                    g_launch.row_hole_begin = top_end;
+                    g_launch.row_hole_end = bot_begin;
                     sweep(a, b, band);
-                    g_row_hole_begin = g_row_hole_end = 0;
+                    g_launch.row_hole_begin = g_launch.row_hole_end = 0;
                 } else {
                     sweep(a, top_end, band);
                     sweep(bot_begin, b, band);
                 }
-                hipEvent_t banded = record(band);
+                hipEvent_t banded = kit.record(band);
                 if (st->n_ranks > 1 && rc == STSTHIP_OK) {
-                    wait(st->comm_stream, banded);
+                    kit.wait(st->comm_stream, banded);
                     rc = strip_exchange(*st, st->current ^ 1, next);
-                    ghosts_ready = record(st->comm_stream);
+                    ghosts_ready = kit.record(st->comm_stream);
                 }
                 sweep_rows(top_end, bot_begin);
-                wait(lane, banded); // the next launch reads the bands' rows
+                kit.wait(lane, banded); // the next launch reads the bands' rows
                 if (lane_low)
-                    wait(lane_low, banded);
+                    kit.wait(lane_low, banded);
             } else {
                 sweep_rows(lo, hi);
             }
@@ -2739,22 +2791,11 @@ int ststhip_strip_advance(ststhip_strip strip, uint64_t iteration_offset, uint64
             iteration += depth;
         }
     }
-    g_tdv_table = nullptr;
-    g_tdv_count = 0;
     // the compute stream is the one callers synchronise with
-    if (band)
-        wait(lane, record(band));
-    if (lane_low)
-        wait(lane, record(lane_low));
-    wait(lane, record(st->comm_stream));
-    g_launch_concurrency = 1;
-    if (rc == STSTHIP_OK && blocking) {
-        hipError_t err = hipStreamSynchronize(lane);
-        if (err != hipSuccess)
-            rc = hip_fail(err, "hipStreamSynchronize");
-    }
-    if (tdv_table)
-        ststhip_free_async(tdv_table, lane); // every stream has been joined into the compute stream above
+    kit.join(lane, {band, lane_low, st->comm_stream});
+    if (rc == STSTHIP_OK && blocking)
+        kit.ordered(hipStreamSynchronize(lane), "hipStreamSynchronize");
+    values.close(lane);
     return rc; // the events go back to the pool (EventPool)
 }
 
@@ -2848,26 +2889,10 @@ int block_exchange(Strip &st, int set, std::uint64_t g) {
                     return rc2;
         }
     }
-    if (has_up || has_down) {
-        // whole buffer rows, ghost columns included: what the left and right neighbours have just delivered goes on to
-        // the blocks above and below -- their corners
-        const void *send_up[16], *send_down[16];
-        void *recv_up[16], *recv_down[16];
-        std::size_t row_bytes[16];
-        const std::uint64_t o_start = st.ghost, o_stop = st.ghost + owned_rows;
-        for (unsigned p = 0; p < st.n_planes; p++) {
-            row_bytes[p] = std::size_t(st.dom.pitch) * st.elem[p];
-            unsigned char *base = static_cast<unsigned char *>(st.planes[set][p]);
-            send_up[p] = base + o_start * row_bytes[p];
-            recv_up[p] = base + (o_start - g) * row_bytes[p];
-            send_down[p] = base + (o_stop - g) * row_bytes[p];
-            recv_down[p] = base + o_stop * row_bytes[p];
-        }
-        if (st.comm)
-            return ststhip_comm_exchange_rows(st.comm, int(st.n_planes), send_up, send_down, recv_up, recv_down, row_bytes,
-                                              std::size_t(g), s);
-        return st.exchange(st.exchange_ctx, int(st.n_planes), send_up, send_down, recv_up, recv_down, row_bytes, std::size_t(g), s);
-    }
+    // whole buffer rows, ghost columns included: what the left and right neighbours have just delivered goes on to
+    // the blocks above and below -- their corners
+    if (has_up || has_down)
+        return exchange_rows(st, set, g);
     return STSTHIP_OK;
 }
 
@@ -2880,41 +2905,13 @@ int block_advance(Strip *st, std::uint64_t iteration_offset, std::uint64_t n_gen
     st->resolved.set_run(iteration_offset, n_generations);
     const std::uint64_t hpg = d.halo_depth_per_generation;
     const std::size_t m = std::size_t(st->exchange_every);
-    int rc = STSTHIP_OK;
-    EventPool events;
-    auto ordered = [&](hipError_t err, const char *what) {
-        if (err != hipSuccess && rc == STSTHIP_OK)
-            rc = hip_fail(err, what);
-    };
-    auto record = [&](hipStream_t on) {
-        hipEvent_t ev = events.take();
-        if (!ev)
-            ordered(hipErrorUnknown, "hipEventCreateWithFlags");
-        else
-            ordered(hipEventRecord(ev, on), "hipEventRecord");
-        return ev;
-    };
-    auto wait = [&](hipStream_t who, hipEvent_t ev) {
-        if (ev)
-            ordered(hipStreamWaitEvent(who, ev, 0), "hipStreamWaitEvent");
-    };
+    LaunchStateGuard idle_on_return;
+    OrderKit kit;
+    int &rc = kit.rc;
     hipStream_t lane = st->compute;
-    g_launch_concurrency = 1;
-    void *tdv_table = nullptr;
-    if (d.tdv_size > 0 && d.fill_tdv) {
-        const std::size_t bytes = std::size_t(d.tdv_size) * n_generations;
-        rc = ststhip_malloc_async(&tdv_table, bytes, lane);
-        if (rc == STSTHIP_OK) {
-            std::vector<unsigned char> values(bytes);
-            d.fill_tdv(st->resolved.ctx, iteration_offset, n_generations, values.data());
-            ordered(hipMemcpyAsync(tdv_table, values.data(), bytes, hipMemcpyHostToDevice, lane), "hipMemcpyAsync");
-            ordered(hipStreamSynchronize(lane), "hipStreamSynchronize"); // `values` is pageable and goes out of scope
-            g_tdv_table = tdv_table;
-            g_tdv_first = iteration_offset;
-            g_tdv_count = n_generations;
-            g_tdv_size = d.tdv_size;
-        }
-    }
+    g_launch.concurrency = 1;
+    ValuesTable values;
+    values.open(d, st->resolved.ctx, iteration_offset, n_generations, lane, kit);
     auto group_depth = [&](std::size_t first) {
         std::uint64_t sum = 0;
         for (std::size_t i = first; i < std::min(first + m, depths.size()); i++)
@@ -2924,16 +2921,16 @@ int block_advance(Strip *st, std::uint64_t iteration_offset, std::uint64_t n_gen
     const bool has_left = st->mesh_c > 0, has_right = st->mesh_c + 1 < st->mesh_cols;
     const bool has_up = st->mesh_r > 0, has_down = st->mesh_r + 1 < st->mesh_rows;
     const bool alone = st->mesh_rows * st->mesh_cols == 1;
-    wait(st->comm_stream, record(lane)); // everything queued so far: a previous advance, uploads, the table
+    kit.wait(st->comm_stream, kit.record(lane)); // everything queued so far: a previous advance, uploads, the table
     hipEvent_t ghosts_ready = nullptr;
     if (!alone && rc == STSTHIP_OK) {
         rc = block_exchange(*st, st->current, group_depth(0));
-        ghosts_ready = record(st->comm_stream);
+        ghosts_ready = kit.record(st->comm_stream);
     }
     std::uint64_t iteration = iteration_offset;
     for (std::size_t first = 0; first < depths.size() && rc == STSTHIP_OK; first += m) {
         const std::size_t last = std::min(first + m, depths.size()) - 1;
-        wait(lane, ghosts_ready);
+        kit.wait(lane, ghosts_ready);
         std::uint64_t widen = group_depth(first);
         for (std::size_t i = first; i <= last && rc == STSTHIP_OK; i++) {
             const std::uint32_t depth = depths[i];
@@ -2942,31 +2939,25 @@ int block_advance(Strip *st, std::uint64_t iteration_offset, std::uint64_t n_gen
             const std::uint64_t hi = has_down ? std::min(st->row_end + widen, st->total_rows) : st->row_end;
             const std::uint64_t clo = has_left ? st->col_begin - std::min(widen, st->col_begin) : st->col_begin;
             const std::uint64_t chi = has_right ? std::min(st->col_end + widen, st->total_cols) : st->col_end;
-            g_col_begin = clo;
-            g_col_end = chi;
+            g_launch.col_begin = clo;
+            g_launch.col_end = chi;
             rc = st->resolved.trampoline(st->resolved.ctx, &st->dom, const_cast<const void *const *>(st->planes[st->current]),
                                          st->planes[st->current ^ 1], lo, hi, iteration, depth, lane);
-            g_col_begin = g_col_end = 0;
+            g_launch.col_begin = g_launch.col_end = 0;
             st->n_launches++;
             st->current ^= 1;
             iteration += depth;
         }
         if (last + 1 < depths.size() && !alone && rc == STSTHIP_OK) {
-            wait(st->comm_stream, record(lane));
+            kit.wait(st->comm_stream, kit.record(lane));
             rc = block_exchange(*st, st->current, group_depth(last + 1));
-            ghosts_ready = record(st->comm_stream);
+            ghosts_ready = kit.record(st->comm_stream);
         }
     }
-    g_tdv_table = nullptr;
-    g_tdv_count = 0;
-    wait(lane, record(st->comm_stream));
-    if (rc == STSTHIP_OK && blocking) {
-        hipError_t err = hipStreamSynchronize(lane);
-        if (err != hipSuccess)
-            rc = hip_fail(err, "hipStreamSynchronize");
-    }
-    if (tdv_table)
-        ststhip_free_async(tdv_table, lane);
+    kit.join(lane, {st->comm_stream});
+    if (rc == STSTHIP_OK && blocking)
+        kit.ordered(hipStreamSynchronize(lane), "hipStreamSynchronize");
+    values.close(lane);
     return rc;
 }
 } // namespace
@@ -2999,26 +2990,11 @@ void place_block(Strip *st, std::uint64_t total_rows, std::uint64_t total_cols, 
 
 // ghost depths, buffers and streams of a block whose sweep (st->resolved) is known; owns `st` from here on
 int finish_block(Strip *st, ststhip_strip *block) {
-    const std::uint64_t total_rows = st->total_rows, total_cols = st->total_cols;
-    const int mesh_rows = st->mesh_rows, mesh_cols = st->mesh_cols;
-    int rc = STSTHIP_OK;
-    const ststhip_sweep_desc &d = st->resolved.desc;
-    st->n_planes = d.n_planes;
-    st->g_max = std::uint64_t(d.alt_generations && d.alt_generations < d.max_generations ? d.alt_generations : d.max_generations) *
-                d.halo_depth_per_generation;
-    std::uint64_t thinnest = std::min(total_rows / mesh_rows, total_cols / mesh_cols);
-    int every = 1;
-    if (st->n_ranks > 1) {
-        every = opt().exchange_every > 0 ? std::min(opt().exchange_every, 16) : 2;
-        while (every > 1 && thinnest < 4 * st->g_max * std::uint64_t(every))
-            every--;
-    }
-    st->exchange_every = every;
-    st->ghost = st->g_max * std::uint64_t(every);
-    if (st->n_ranks > 1 && thinnest < 2 * st->ghost) {
+    if (int rc = plan_ghosts(st, std::min(st->total_rows / st->mesh_rows, st->total_cols / st->mesh_cols), 2,
+                             "blocks are thinner than two ghost depths: use a smaller mesh, a larger grid or a "
+                             "smaller STSTHIP_EXCHANGE_EVERY")) {
         delete st;
-        return fail(STSTHIP_ERR_INVALID, "blocks are thinner than two ghost depths: use a smaller mesh, a larger grid or a "
-                                         "smaller STSTHIP_EXCHANGE_EVERY");
+        return rc;
     }
     // ghost columns: the exchanged depth, and a few more so that the strips next to the block's sides run the check-free
     // code (a wave's footprint is rounded up to whole lanes); the extra columns are never exchanged and never matter
@@ -3027,40 +3003,19 @@ int finish_block(Strip *st, ststhip_strip *block) {
     st->local_rows = (st->row_end - st->row_begin) + 2 * st->ghost;
     st->col_origin = std::int64_t(st->col_begin) - std::int64_t(st->ghost_cols);
     st->local_cols = (st->col_end - st->col_begin) + 2 * st->ghost_cols;
-    st->dom = ststhip_domain{};
-    st->dom.global_height = total_rows;
-    st->dom.global_width = total_cols;
+    st->dom = whole_grid(st->total_rows, st->total_cols);
     st->dom.row_origin = st->row_origin;
     st->dom.local_rows = st->local_rows;
     st->dom.pitch = st->local_cols;
     st->dom.col_origin = st->col_origin;
     st->dom.local_cols = st->local_cols;
-    hipError_t err = hipStreamCreateWithFlags(&st->compute, hipStreamNonBlocking);
-    if (err == hipSuccess)
-        err = hipStreamCreateWithFlags(&st->comm_stream, hipStreamNonBlocking);
-    for (int set = 0; set < 2 && err == hipSuccess && rc == STSTHIP_OK; set++)
-        for (unsigned p = 0; p < st->n_planes && rc == STSTHIP_OK; p++) {
-            st->elem[p] = d.plane_elem_size[p];
-            const std::size_t bytes = std::size_t(st->local_rows) * st->local_cols * st->elem[p];
-            rc = ststhip_malloc_async(&st->planes[set][p], bytes, st->compute);
-            if (rc == STSTHIP_OK)
-                err = hipMemsetAsync(st->planes[set][p], 0, bytes, st->compute);
-        }
+    int rc = create_streams_and_buffers(st, false, "block set-up");
     if (st->mesh_cols > 1)
         for (int side = 0; side < 4 && rc == STSTHIP_OK; side++)
             for (unsigned p = 0; p < st->n_planes && rc == STSTHIP_OK; p++)
                 rc = ststhip_malloc_async(&st->stage[side][p], std::size_t(st->row_end - st->row_begin) * st->ghost * st->elem[p],
                                           st->compute);
-    if (err != hipSuccess)
-        rc = hip_fail(err, "block set-up");
-    if (rc == STSTHIP_OK && (err = hipStreamSynchronize(st->compute)) != hipSuccess)
-        rc = hip_fail(err, "block set-up");
-    if (rc != STSTHIP_OK) {
-        ststhip_strip_destroy(st);
-        return rc;
-    }
-    *block = st;
-    return STSTHIP_OK;
+    return hand_out(st, rc, "block set-up", block);
 }
 } // namespace
 } // extern "C++"
@@ -3080,21 +3035,12 @@ int ststhip_block_create(const char *app, const void *tf_params, const void *hal
     if (int rc = ststhip_init(-1))
         return rc;
     Strip *st = new Strip;
-    st->app = app;
-    st->params.assign(static_cast<const unsigned char *>(tf_params),
-                      static_cast<const unsigned char *>(tf_params) + std::max<std::uint32_t>(e->info.params_size, 1));
-    st->halo.assign(static_cast<const unsigned char *>(halo_cell), static_cast<const unsigned char *>(halo_cell) + e->info.cell_size);
     place_block(st, total_rows, total_cols, rank, mesh_rows, mesh_cols, comm, exchange_rows, exchange_rows_ctx, exchange_cols,
                 exchange_cols_ctx);
-    ststhip_domain whole = {};
-    whole.global_height = total_rows;
-    whole.global_width = total_cols;
-    whole.pitch = total_cols;
-    whole.local_rows = total_rows;
-    whole.local_cols = total_cols; // (a block: the sweeps run on cells, never on the packed words of the Game of Life)
+    // (a block names its columns: the sweeps run on cells, never on the packed words of the Game of Life)
+    const ststhip_domain whole = whole_grid(total_rows, total_cols, true);
     const ststhip_domain *dom = &whole;
-    int rc = resolve_app(st->resolved, st->app.c_str(), st->params.data(), st->halo.data(), dom, nullptr, nullptr, false);
-    if (rc != STSTHIP_OK) {
+    if (int rc = use_app_sweep(st, e, app, tf_params, halo_cell, dom)) {
         delete st;
         return rc;
     }
@@ -3115,10 +3061,7 @@ int ststhip_block_create_custom(ststhip_sweep_fn sweep, void *ctx, const ststhip
     Strip *st = new Strip;
     place_block(st, total_rows, total_cols, rank, mesh_rows, mesh_cols, comm, exchange_rows, exchange_rows_ctx, exchange_cols,
                 exchange_cols_ctx);
-    st->resolved.entry = nullptr; // the caller's sweep: no registry entry, no run window to maintain
-    st->resolved.trampoline = sweep;
-    st->resolved.ctx = ctx;
-    st->resolved.desc = *desc;
+    use_custom_sweep(st, sweep, ctx, desc);
     return finish_block(st, block);
 }
 

@@ -2,7 +2,7 @@
 
 The driver takes its launch as a callback.  A test hands it one that records every launch it is asked for as a `Launch`
 and hands the list to `check_schedule`, which knows nothing of the driver's code: only what any correct schedule of
-whole-grid passes must look like.  Pure Python, no GPU, no library (tests/test_pass_schedule.py proves on hand-made
+whole-grid passes must look like.  Pure Python, no GPU, no library of its own (tests/test_pass_schedule.py proves on hand-made
 schedules that it accepts correct ones and rejects each kind of wrong one).
 
 I6 is checked row-wise, on purpose: a launch may be told that its target holds the constant fields if an earlier pass
@@ -55,6 +55,16 @@ class Launch:
         hole = f" hole {self.hole}" if self.hole[0] < self.hole[1] else ""
         return (f"launch #{self.order} (generation {self.iteration} + {self.n_generations}, rows "
                 f"[{self.out_row_begin}, {self.out_row_end}){hole}, stream {self.stream:#x})")
+
+
+def assert_launch_state_idle(capi):
+    """The calling thread's launch state between driver calls, read through `capi` (stencilstream_amd.capi): what every
+    way out of ststhip_run_passes, ststhip_strip_advance and the block driver leaves behind."""
+    assert capi.launch_concurrency() == 1
+    assert capi.target_holds_constants() == 0
+    assert capi.launch_row_hole() == (0, 0)
+    base, _first, n_values, _size = capi.current_tdv_table()
+    assert (base, n_values) == (0, 0)
 
 
 def halvings(max_generations, cap=0):

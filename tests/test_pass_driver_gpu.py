@@ -17,7 +17,7 @@ import time
 import numpy as np
 import pytest
 
-from pass_schedule import Launch, check_schedule, check_tile_frontiers, halvings
+from pass_schedule import Launch, assert_launch_state_idle, check_schedule, check_tile_frontiers, halvings
 
 pytestmark = pytest.mark.gpu
 
@@ -347,6 +347,49 @@ def test_values_table_of_the_call(workload, monkeypatch):
     run.check(expect_tdv=True)
     assert asked == [(7, 37)]
     assert {l.tdv[1:] for l in run.launches} == {(7, 37, 8)} and len({l.tdv[0] for l in run.launches}) == 1
+
+
+def test_launch_state_is_idle_after_a_call(workload, monkeypatch):
+    """Whichever way a call leaves the driver -- done, refused, or ended by its callback -- the calling thread's launch
+    state is idle afterwards: one launch at a time, no constants in the target, no row hole, no values table."""
+    import torch
+
+    from stencilstream_amd import capi
+
+    set_scheme(monkeypatch, 2, "moving")
+    w = workload("hotspot", BIG)
+    run = record(w, w.desc(), 37)
+    assert {l.concurrency for l in run.launches} == {2} and any(l.target_holds_constants for l in run.launches)
+    assert_launch_state_idle(capi)
+
+    w = workload("jacobi5general", BIG)
+    desc, fill_fn = w.desc(), capi.FILL_TDV_FN(lambda _ctx, offset, n, values: None)
+    desc.tdv_size = 8
+    desc.fill_tdv = fill_fn
+    run = record(w, desc, 37, 7)
+    assert all(l.tdv[0] != 0 and l.tdv[1:] == (7, 37, 8) for l in run.launches)
+    assert_launch_state_idle(capi)
+
+    # refused: a second depth the sweep is not compiled for
+    with pytest.raises(capi.StsthipError):
+        record(w, w.desc(6, next(_keys)), 37)
+    assert_launch_state_idle(capi)
+
+    # the callback raises on its third launch (the two before it are real launches)
+    seen = []
+
+    def sweep(dom, src, dst, out_begin, out_end, iteration, depth, stream):
+        seen.append((capi.launch_concurrency(), capi.current_tdv_table()[0]))
+        if len(seen) == 3:
+            raise RuntimeError("third launch")
+        capi.app_sweep(w.app, w.params, w.halo, dom, src, dst, out_begin, out_end, iteration, depth, stream)
+
+    with pytest.raises(RuntimeError, match="third launch"):
+        capi.run_passes(sweep, desc, w.dom, [t.data_ptr() for t in w.src], [t.data_ptr() for t in w.dst], 0, 37,
+                        blocking=True, stream=w.stream.cuda_stream)
+    torch.cuda.synchronize()
+    assert len(seen) == 3 and all(c == 2 and base != 0 for c, base in seen)
+    assert_launch_state_idle(capi)
 
 
 # ------------------------------------------------------------------------------------------------ b. the probe

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from pass_schedule import assert_launch_state_idle
+
 pytestmark = pytest.mark.gpu
 
 
@@ -309,6 +311,7 @@ def test_strip_driver_over_rccl_loopback(gpu, oracle, monkeypatch, every):
             strip.warm_up()
             strip.advance(0, n_first)
             strip.advance(n_first, n_second, blocking=True)
+            assert_launch_state_idle(capi)
             results.append([strip.download(i, dt) for i, dt in planes])
             launches, exchanges = strip.counters()
             assert exchanges >= 3
@@ -396,6 +399,7 @@ def test_single_block_equals_oracle(gpu, oracle):
         block.upload(0, grid)
         block.advance(0, 29)
         block.advance(29, 8, blocking=True)
+        assert_launch_state_idle(capi)
         want = oracle.jacobi("Jacobi5General", coef, grid, 37, halo=halo, n_threads=8)
         assert np.array_equal(bits(block.download(0, np.float32)), bits(want)), f"jacobi {coef[0]}"
         block.close()
@@ -405,6 +409,26 @@ def test_single_block_equals_oracle(gpu, oracle):
     block.advance(0, 19, blocking=True)
     assert np.array_equal(block.download(0, np.uint8), oracle.conway(life, 19, n_threads=8))
     block.close()
+
+
+def test_block_with_a_bad_description_is_refused(gpu):
+    """ststhip_block_create_custom checks the sweep's description as ststhip_strip_create_custom does: the number of
+    planes indexes arrays of 16."""
+    import ctypes as C
+
+    from stencilstream_amd import capi
+
+    capi.init(0)
+    lib = capi.load()
+    never_called = capi.SWEEP_FN(lambda *_: 2)
+    for n_planes, max_generations in ((0, 8), (17, 8)):
+        desc = capi.SweepDesc()
+        desc.n_planes, desc.max_generations, desc.halo_depth_per_generation = n_planes, max_generations, 1
+        handle = C.c_void_p()
+        status = lib.ststhip_block_create_custom(never_called, None, C.byref(desc), 64, 64, 0, 1, 1, None, None, None, None,
+                                                 None, C.byref(handle))
+        assert status == 2 and "bad sweep description" in capi.last_error()  # STSTHIP_ERR_INVALID
+        assert not handle.value
 
 
 def _mesh_rank(rank, mesh_rows, mesh_cols, port, result_dir):
