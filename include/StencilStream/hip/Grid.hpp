@@ -266,6 +266,14 @@ template <typename Cell> class Grid {
         storage->host_valid = false;
         return static_cast<Cell *>(storage->device);
     }
+    // AoS cells in HBM about to be changed in part by work on the runtime's stream (hip/Region.hpp): the device copy
+    // is brought up to date first, a pending upload is waited for, and the host mirror no longer counts -- the next
+    // GridAccessor downloads again, the next StencilUpdate uploads nothing.
+    Cell *device_cells_for_update() {
+        storage->sync_to_device();
+        storage->host_valid = false;
+        return static_cast<Cell *>(storage->device);
+    }
 
   private:
     void require_same_extent(sycl::range<2> other) const {

@@ -268,6 +268,73 @@ int ststhip_grid_norms(int n_fields, const ststhip_norm_field *fields, ststhip_n
 int ststhip_grid_distance(int n_fields, const ststhip_norm_field *fields, const void *const *other_base,
                           ststhip_norm_result *result, ststhip_stream stream);
 
+/* Grid regions: move a rectangle of a grid, or of one member of its cells, where the cells are -- device to device,
+ * a constant into a rectangle, or between HBM and host memory without the rest of the grid (an extension, as the
+ * norms; additive within ABI 6).  What a host that looks at its grid or nudges it between two updates needs: one
+ * member of every cell for a frame (optionally every k-th row and column), a source injected into a handful of cells.
+ *
+ * A view is the byte geometry of ststhip_norm_field: the element of cell (r, c) is the `elem_size` bytes at
+ * base + (r * pitch + c) * stride.  A member of an AoS cell (base = cells + offset of the member, stride =
+ * sizeof(Cell)), a whole cell (elem_size = stride = sizeof(Cell)), a per-field plane (stride = elem_size), a grid of
+ * bools and host memory with any row pitch are all views.  Bytes are moved verbatim: NaN payloads, signed zeros and
+ * padding the caller names arrive unchanged.  Nothing needs to be aligned: base, stride and elem_size are arbitrary,
+ * the kernels pick the widest access all of them allow and the result is the same for every width.
+ *
+ * Element (i, j) of the n_rows x n_cols rectangle is read from source cell (src_row + i * src_row_step,
+ * src_col + j * src_col_step) and lands in destination cell (dst_row + i, dst_col + j).  Nothing is clipped: a
+ * rectangle that leaves its view is an error.  An empty rectangle (n_rows == 0 or n_cols == 0) succeeds on the host,
+ * also with a null base and without a device.
+ *
+ * One to eight entries per call.  The entries of one call run in NO particular order and are not checked against each
+ * other: a caller must not let one entry write what another entry reads or writes.
+ *
+ * Limits, so that a lane's offset inside a row fits 32 bits: n_rows and n_cols are below 2^31, and so is the byte extent
+ * of a rectangle's row in either view, n_cols * src_col_step * src.stride and n_cols * dst.stride.
+ *
+ * Source and destination of one entry may share memory in one way only.  If the byte spans of the two rectangles
+ * (first byte of the first element to last byte of the last) intersect, the entry is accepted only when both views
+ * have the same stride and pitch, both steps are 1 and the destination's first element lies d bytes behind or in front
+ * of the source's with elem_size <= d and d + elem_size <= stride: one member of a cell copied to another member of
+ * the same cells.  Everything else that intersects is refused.
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID, ststhip_last_error() starts with
+ * "grid region"): n outside 1..8, elem_size outside 1..128 or above a stride, stride 0, pitch < width, a step of 0, a
+ * null base with a non-empty rectangle, a null `value`, extents that describe more than 2^63 bytes, a rectangle outside
+ * its view, the limits and the overlap rule above.
+ *
+ * ststhip_grid_copy (device to device) and ststhip_grid_fill are ordered on `stream` and do not synchronise;
+ * `value` is read inside the call.  ststhip_grid_download packs the rectangle on the device into pooled staging,
+ * copies that to the host and synchronises `stream` before it returns; dst is host memory, dense within a row
+ * (dst.stride == elem_size), rows dst.pitch elements apart.  ststhip_grid_upload is its mirror: src is host memory
+ * (src.stride == elem_size, both steps 1, any pitch), copied to pooled staging and unpacked from there; it
+ * synchronises `stream`, so the caller's buffer is free on return. */
+typedef struct {
+    void *base;        /* the element of cell (0, 0)                         */
+    uint64_t stride;   /* bytes between neighbouring cells of a row          */
+    uint64_t pitch;    /* cells between neighbouring rows (>= width)         */
+    uint64_t height, width;
+} ststhip_grid_view;
+typedef struct {
+    ststhip_grid_view dst, src;
+    uint32_t elem_size;              /* bytes moved per cell, 1 .. 128        */
+    uint32_t reserved;               /* 0                                     */
+    uint64_t dst_row, dst_col;       /* where element (0, 0) of the rectangle lands */
+    uint64_t src_row, src_col;       /* the first cell read                   */
+    uint64_t n_rows, n_cols;         /* elements moved per axis               */
+    uint64_t src_row_step, src_col_step; /* >= 1: element (i, j) comes from source cell
+                                        (src_row + i*row_step, src_col + j*col_step) */
+} ststhip_grid_copy_desc;
+typedef struct {
+    ststhip_grid_view dst;
+    uint32_t elem_size, reserved;
+    uint64_t dst_row, dst_col, n_rows, n_cols;
+    const void *value;               /* elem_size bytes, host memory, read inside the call */
+} ststhip_grid_fill_desc;
+int ststhip_grid_copy(int n, const ststhip_grid_copy_desc *copies, ststhip_stream stream);
+int ststhip_grid_fill(int n, const ststhip_grid_fill_desc *fills, ststhip_stream stream);
+int ststhip_grid_download(int n, const ststhip_grid_copy_desc *copies, ststhip_stream stream);
+int ststhip_grid_upload(int n, const ststhip_grid_copy_desc *copies, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

@@ -177,6 +177,29 @@ class NormResult(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class GridView(C.Structure):
+    """ststhip_grid_view"""
+
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_uint64), ("pitch", C.c_uint64), ("height", C.c_uint64),
+                ("width", C.c_uint64)]
+
+
+class GridCopyDesc(C.Structure):
+    """ststhip_grid_copy_desc"""
+
+    _fields_ = [("dst", GridView), ("src", GridView), ("elem_size", C.c_uint32), ("reserved", C.c_uint32),
+                ("dst_row", C.c_uint64), ("dst_col", C.c_uint64), ("src_row", C.c_uint64), ("src_col", C.c_uint64),
+                ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("src_row_step", C.c_uint64),
+                ("src_col_step", C.c_uint64)]
+
+
+class GridFillDesc(C.Structure):
+    """ststhip_grid_fill_desc"""
+
+    _fields_ = [("dst", GridView), ("elem_size", C.c_uint32), ("reserved", C.c_uint32), ("dst_row", C.c_uint64),
+                ("dst_col", C.c_uint64), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("value", C.c_void_p)]
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -265,6 +288,10 @@ def load():
         "ststhip_reduce_max_abs": [vp, sz, u64, u64, u64, C.c_int, C.POINTER(ReduceField), C.POINTER(C.c_double), vp],
         "ststhip_grid_norms": [C.c_int, C.POINTER(NormField), C.POINTER(NormResult), vp],
         "ststhip_grid_distance": [C.c_int, C.POINTER(NormField), pp, C.POINTER(NormResult), vp],
+        "ststhip_grid_copy": [C.c_int, C.POINTER(GridCopyDesc), vp],
+        "ststhip_grid_fill": [C.c_int, C.POINTER(GridFillDesc), vp],
+        "ststhip_grid_download": [C.c_int, C.POINTER(GridCopyDesc), vp],
+        "ststhip_grid_upload": [C.c_int, C.POINTER(GridCopyDesc), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -647,6 +674,59 @@ def grid_norms(fields, other=None, stream=0):
         check(lib.ststhip_grid_distance(n, table, _ptr_array(other), result, C.c_void_p(int(stream))),
               "ststhip_grid_distance")
     return result
+
+
+def grid_view(base, stride, height, width, pitch=None):
+    """A ststhip_grid_view: the element of cell (r, c) lies at base + (r * pitch + c) * stride bytes.  A member of an
+    AoS cell: base = cells + its offset, stride = the cell's size; a plane or host rows: stride = the element's size."""
+    return GridView(C.c_void_p(int(base) or None), int(stride), int(width if pitch is None else pitch), int(height),
+                    int(width))
+
+
+def grid_copy_desc(dst, src, elem_size, n_rows, n_cols, dst_at=(0, 0), src_at=(0, 0), step=(1, 1)):
+    """A ststhip_grid_copy_desc: element (i, j) of the n_rows x n_cols rectangle comes from cell
+    (src_at[0] + i * step[0], src_at[1] + j * step[1]) of view `src` and lands in cell (dst_at[0] + i, dst_at[1] + j)
+    of view `dst`; elem_size bytes each."""
+    return GridCopyDesc(dst, src, int(elem_size), 0, int(dst_at[0]), int(dst_at[1]), int(src_at[0]), int(src_at[1]),
+                        int(n_rows), int(n_cols), int(step[0]), int(step[1]))
+
+
+def grid_fill_desc(dst, value, n_rows, n_cols, dst_at=(0, 0)):
+    """A ststhip_grid_fill_desc: the bytes `value` (one element) into every cell of the rectangle of view `dst`."""
+    value = bytes(value)
+    desc = GridFillDesc(dst, len(value), 0, int(dst_at[0]), int(dst_at[1]), int(n_rows), int(n_cols), None)
+    desc._value = C.create_string_buffer(value, len(value))  # kept alive with the description
+    desc.value = C.cast(desc._value, C.c_void_p)
+    return desc
+
+
+def _grid_region_call(name, kind, descs, stream):
+    descs = list(descs)
+    table = (kind * max(len(descs), 1))(*descs)  # (the descriptions, and the values they own, outlive the call)
+    check(getattr(load(), name)(len(descs), table, C.c_void_p(int(stream))), name)
+
+
+def grid_copy(copies, stream=0):
+    """ststhip_grid_copy: 1..8 grid_copy_desc() entries, device to device, queued on `stream`; does not synchronise.
+    The entries run in no particular order."""
+    _grid_region_call("ststhip_grid_copy", GridCopyDesc, copies, stream)
+
+
+def grid_fill(fills, stream=0):
+    """ststhip_grid_fill: 1..8 grid_fill_desc() entries, queued on `stream`; does not synchronise."""
+    _grid_region_call("ststhip_grid_fill", GridFillDesc, fills, stream)
+
+
+def grid_download(copies, stream=0):
+    """ststhip_grid_download: the destination views are host memory, dense within a row (stride = elem_size, any
+    pitch).  Returns when the bytes are there."""
+    _grid_region_call("ststhip_grid_download", GridCopyDesc, copies, stream)
+
+
+def grid_upload(copies, stream=0):
+    """ststhip_grid_upload: the source views are host memory (stride = elem_size, steps 1, any pitch); the host
+    memory may be reused when the call returns."""
+    _grid_region_call("ststhip_grid_upload", GridCopyDesc, copies, stream)
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -170,6 +170,98 @@ class Grid:
         return {name: Norms(r.n_cells, r.n_nonfinite, r.max_abs, r.sum, r.sum_abs, r.sum_sq)
                 for (name, _, _), r in zip(members, result)}
 
+    # ---- parts of the grid, moved where the cells are (ststhip_grid_download / _upload / _fill / _copy) ----
+    @staticmethod
+    def _axis(given, extent, what):
+        """(begin, end) of a range of rows or columns; None = the whole axis.  Nothing is clipped."""
+        begin, end = (0, extent) if given is None else (int(given[0]), int(given[1]))
+        if not 0 <= begin <= end <= extent:
+            raise ValueError(f"{what} {begin}:{end} leave the grid ({extent})")
+        return begin, end
+
+    @staticmethod
+    def _steps(step):
+        rows, cols = int(step[0]), int(step[1])
+        if rows < 1 or cols < 1:
+            raise ValueError("a step is 1 or more")
+        return rows, cols
+
+    def _element(self, field):
+        """(dtype, byte offset in the cell) of what a region call moves: the whole cell, or the member `field`."""
+        if field is None:
+            return self.cell_dtype, 0
+        if self.cell_dtype.names is None or field not in self.cell_dtype.names:
+            raise ValueError(f"the cell has no field {field!r}")
+        return self.cell_dtype.fields[field][0], self.cell_dtype.fields[field][1]
+
+    def _view(self, offset=0):
+        return capi.grid_view(self.cells.data_ptr() + offset, self.cell_dtype.itemsize, self.height, self.width)
+
+    def _on_device(self):
+        capi.init(self.device.index if self.device.index is not None else -1)
+        return capi.on_stream(self.device)
+
+    def read(self, rows=None, cols=None, step=(1, 1), field=None):
+        """The cells of rows[0]:rows[1]:step[0], cols[0]:cols[1]:step[1] (None = the whole axis), or their member
+        `field`, as a numpy array -- what to_numpy()[r0:r1:sr, c0:c1:sc] (or that [field]) holds, without bringing
+        the rest of the grid to the host.  A range that leaves the grid raises ValueError."""
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        sr, sc = self._steps(step)
+        kind, offset = self._element(field)
+        n_rows, n_cols = -(-(r1 - r0) // sr), -(-(c1 - c0) // sc)
+        out = np.empty((n_rows, n_cols), dtype=kind)
+        if out.size:
+            with self._on_device() as torch_stream:
+                host = capi.grid_view(out.ctypes.data, kind.itemsize, n_rows, n_cols)
+                capi.grid_download([capi.grid_copy_desc(host, self._view(offset), kind.itemsize, n_rows, n_cols,
+                                                        src_at=(r0, c0), step=(sr, sc))], torch_stream.cuda_stream)
+        return out
+
+    def write(self, array, at=(0, 0), field=None):
+        """array (2-D, the cell's dtype or the member's) into the cells from (at[0], at[1]) on, or into their member
+        `field`; the other members keep their bytes.  The array may be reused when the call returns."""
+        kind, offset = self._element(field)
+        array = np.ascontiguousarray(array, dtype=kind)
+        if array.ndim != 2:
+            raise ValueError("a region is two-dimensional")
+        r0, c0 = int(at[0]), int(at[1])
+        self._axis((r0, r0 + array.shape[0]), self.height, "rows")
+        self._axis((c0, c0 + array.shape[1]), self.width, "columns")
+        if array.size:
+            with self._on_device() as torch_stream:
+                host = capi.grid_view(array.ctypes.data, kind.itemsize, array.shape[0], array.shape[1])
+                capi.grid_upload([capi.grid_copy_desc(self._view(offset), host, kind.itemsize, array.shape[0],
+                                                      array.shape[1], dst_at=(r0, c0))], torch_stream.cuda_stream)
+
+    def fill(self, value, rows=None, cols=None, field=None):
+        """One value (a cell, or a member `field`) into every cell of rows[0]:rows[1], cols[0]:cols[1]; its bytes
+        arrive as they are (NaN payloads, -0.0).  Queued behind the work on the grid; does not wait."""
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        kind, offset = self._element(field)
+        cell = np.zeros((), dtype=kind)
+        cell[...] = value
+        if r1 > r0 and c1 > c0:
+            with self._on_device() as torch_stream:
+                capi.grid_fill([capi.grid_fill_desc(self._view(offset), cell.tobytes(), r1 - r0, c1 - c0,
+                                                    dst_at=(r0, c0))], torch_stream.cuda_stream)
+
+    def paste(self, source, rows=None, cols=None, at=(0, 0), step=(1, 1)):
+        """The cells rows[0]:rows[1]:step[0], cols[0]:cols[1]:step[1] of grid `source` (same cell type) into this grid
+        from (at[0], at[1]) on, device to device.  Queued; does not wait."""
+        if source.cell_dtype != self.cell_dtype:
+            raise ValueError("the source grid has not the same cell type as the grid")
+        (r0, r1), (c0, c1) = source._axis(rows, source.height, "rows"), source._axis(cols, source.width, "columns")
+        sr, sc = self._steps(step)
+        n_rows, n_cols = -(-(r1 - r0) // sr), -(-(c1 - c0) // sc)
+        a0, a1 = int(at[0]), int(at[1])
+        self._axis((a0, a0 + n_rows), self.height, "rows")
+        self._axis((a1, a1 + n_cols), self.width, "columns")
+        if n_rows and n_cols:
+            with self._on_device() as torch_stream:
+                capi.grid_copy([capi.grid_copy_desc(self._view(), source._view(), self.cell_dtype.itemsize, n_rows,
+                                                    n_cols, dst_at=(a0, a1), src_at=(r0, c0), step=(sr, sc))],
+                               torch_stream.cuda_stream)
+
 
 @dataclass
 class Params:
