@@ -76,6 +76,10 @@ class BlockUpdate {
                         "ststhip_strip_advance");
     }
     void synchronize() { internal::check(ststhip_strip_synchronize(block), "ststhip_strip_synchronize"); }
+    // sweep launches and ghost exchanges since the block was built (ststhip_strip_counters)
+    void counters(std::uint64_t &n_launches, std::uint64_t &n_exchanges) const {
+        internal::check(ststhip_strip_counters(block, &n_launches, &n_exchanges), "ststhip_strip_counters");
+    }
 
   private:
     void transfer(Cell *host_cells, bool to_device) {

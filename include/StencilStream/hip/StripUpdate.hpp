@@ -71,6 +71,10 @@ class StripUpdate {
                         "ststhip_strip_advance");
     }
     void synchronize() { internal::check(ststhip_strip_synchronize(strip), "ststhip_strip_synchronize"); }
+    // sweep launches and ghost exchanges since the strip was built (ststhip_strip_counters)
+    void counters(std::uint64_t &n_launches, std::uint64_t &n_exchanges) const {
+        internal::check(ststhip_strip_counters(strip, &n_launches, &n_exchanges), "ststhip_strip_counters");
+    }
 
   private:
     void transfer(Cell *host_rows, bool to_device) {

@@ -622,7 +622,9 @@ int ststhip_strip_counters(ststhip_strip strip, uint64_t *n_launches, uint64_t *
  * carries the corners --, then every launch of the group sweeps the owned block widened by what the rest of the group
  * still needs.  The minimal form of the reference's tile geometry (StencilStream/tiling/Grid.hpp:305-450): no overlap of
  * exchange and interior (a block's boundary is a frame, not two bands).  mesh_cols = 1 gives the row strips above
- * without their overlap; use ststhip_strip_create for those.
+ * without their overlap; use ststhip_strip_create for those.  Along every axis that is cut (more than one block) a
+ * block must own at least two ghost depths, else STSTHIP_ERR_INVALID; an axis with one block may be as short as the
+ * grid is.
  * `comm`: a communicator of the mesh's ranks whose neighbours are wired for the mesh (ststhip_comm_set_mesh), or
  * NULL and the two callbacks (contract of ststhip_comm_exchange_rows; the column callback gets the packed blocks as
  * "one row" of block bytes: send_up = send_left, send_down = send_right, ...). */

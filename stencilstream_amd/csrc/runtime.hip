@@ -2990,7 +2990,14 @@ void place_block(Strip *st, std::uint64_t total_rows, std::uint64_t total_cols, 
 
 // ghost depths, buffers and streams of a block whose sweep (st->resolved) is known; owns `st` from here on
 int finish_block(Strip *st, ststhip_strip *block) {
-    if (int rc = plan_ghosts(st, std::min(st->total_rows / st->mesh_rows, st->total_cols / st->mesh_cols), 2,
+    // the thinnest extent a block owns along an axis that is cut: an axis with one block has no neighbour, exchanges
+    // nothing and may be as short as the grid is
+    std::uint64_t thinnest = std::max(st->total_rows, st->total_cols);
+    if (st->mesh_rows > 1)
+        thinnest = std::min(thinnest, st->total_rows / st->mesh_rows);
+    if (st->mesh_cols > 1)
+        thinnest = std::min(thinnest, st->total_cols / st->mesh_cols);
+    if (int rc = plan_ghosts(st, thinnest, 2,
                              "blocks are thinner than two ghost depths: use a smaller mesh, a larger grid or a "
                              "smaller STSTHIP_EXCHANGE_EVERY")) {
         delete st;

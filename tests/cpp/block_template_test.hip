@@ -1,5 +1,5 @@
 // stencil::hip::BlockUpdate (the template-level block driver) with USER transition functions: the blocks of a mesh as
-// THREADS of one process on one GPU, ghost columns and rows through an in-process mailbox (RCCL cannot join several ranks
+// THREADS of one process on one GPU, ghost columns and rows through the in-process mailbox of mesh_harness.hpp (RCCL cannot join several ranks
 // on one device; on a box with a GPU per rank the same code passes a communicator instead of the callbacks).  Every mesh's
 // assembled result must equal hip::StencilUpdate on the whole grid, bit for bit.
 //
@@ -7,17 +7,18 @@
 #include <StencilStream/BaseTransitionFunction.hpp>
 #include <StencilStream/hip/BlockUpdate.hpp>
 
-#include <condition_variable>
+#include "mesh_harness.hpp"
+
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
 #include <tuple>
 #include <vector>
 
 using namespace stencil;
+using namespace mesh_harness; // Mesh, Side, exchange_rows, exchange_cols: the in-process mailbox
 
 namespace {
 constexpr std::size_t H = 700, W = 530;
@@ -57,98 +58,6 @@ struct Conduction : public BaseTransitionFunction {
 float ramp_cell(std::size_t r, std::size_t c) { return float((r * 13 + c * 7) % 64) * 0.125f; }
 Plate plate_cell(std::size_t r, std::size_t c) {
     return Plate{float((r * 5 + c * 3) % 97) * 0.25f, 0.0625f + 0.015625f * float((r + 2 * c) % 8)};
-}
-
-#define CHECK(call)                                                                                 \
-    do {                                                                                            \
-        int rc_ = (call);                                                                           \
-        if (rc_ != STSTHIP_OK) {                                                                    \
-            std::fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, ststhip_last_error());         \
-            std::exit(2);                                                                           \
-        }                                                                                           \
-    } while (0)
-
-// one directed edge of the mesh: a buffer of one message
-struct Edge {
-    std::mutex m;
-    std::condition_variable cv;
-    bool full = false;
-    std::vector<std::vector<unsigned char>> planes;
-    void put(int n_planes, const void *const *device, const size_t *row_bytes, size_t n_rows, ststhip_stream stream) {
-        std::vector<std::vector<unsigned char>> message(n_planes);
-        for (int p = 0; p < n_planes; p++) {
-            message[p].resize(row_bytes[p] * n_rows);
-            CHECK(ststhip_memcpy_d2h(message[p].data(), device[p], message[p].size(), stream));
-        }
-        CHECK(ststhip_stream_synchronize(stream));
-        std::unique_lock<std::mutex> lock(m);
-        cv.wait(lock, [&] { return !full; });
-        planes.swap(message);
-        full = true;
-        cv.notify_all();
-    }
-    void take(int n_planes, void *const *device, const size_t *row_bytes, size_t n_rows, ststhip_stream stream) {
-        std::vector<std::vector<unsigned char>> message;
-        {
-            std::unique_lock<std::mutex> lock(m);
-            cv.wait(lock, [&] { return full; });
-            message.swap(planes);
-            full = false;
-            cv.notify_all();
-        }
-        for (int p = 0; p < n_planes; p++) {
-            if (message[p].size() != row_bytes[p] * n_rows) {
-                std::fprintf(stderr, "mailbox: a message of %zu bytes where %zu were expected\n", message[p].size(),
-                             row_bytes[p] * n_rows);
-                std::exit(2);
-            }
-            CHECK(ststhip_memcpy_h2d(device[p], message[p].data(), message[p].size(), stream));
-        }
-        CHECK(ststhip_stream_synchronize(stream));
-    }
-};
-struct Mesh {
-    int rows, cols;
-    std::vector<Edge> to_up, to_down, to_left, to_right; // indexed by the SENDING rank
-    Mesh(int r, int c) : rows(r), cols(c), to_up(r * c), to_down(r * c), to_left(r * c), to_right(r * c) {}
-};
-struct Side {
-    Mesh *mesh;
-    int rank;
-};
-// the contract of ststhip_comm_exchange_rows; "first" / "second" neighbour = up / down for rows, left / right for columns
-int exchange_rows(void *ctx, int n_planes, const void *const *send_up, const void *const *send_down, void *const *recv_up,
-                  void *const *recv_down, const size_t *row_bytes, size_t n_rows, ststhip_stream stream) {
-    Side *s = static_cast<Side *>(ctx);
-    Mesh &m = *s->mesh;
-    const int r = s->rank / m.cols;
-    CHECK(ststhip_stream_synchronize(stream));
-    if (r > 0)
-        m.to_up[s->rank].put(n_planes, send_up, row_bytes, n_rows, stream);
-    if (r + 1 < m.rows)
-        m.to_down[s->rank].put(n_planes, send_down, row_bytes, n_rows, stream);
-    if (r > 0)
-        m.to_down[s->rank - m.cols].take(n_planes, recv_up, row_bytes, n_rows, stream);
-    if (r + 1 < m.rows)
-        m.to_up[s->rank + m.cols].take(n_planes, recv_down, row_bytes, n_rows, stream);
-    return STSTHIP_OK;
-}
-int exchange_cols(void *ctx, int n_planes, const void *const *send_left, const void *const *send_right,
-                  void *const *recv_left, void *const *recv_right, const size_t *row_bytes, size_t n_rows,
-                  ststhip_stream stream) {
-    Side *s = static_cast<Side *>(ctx);
-    Mesh &m = *s->mesh;
-    const int c = s->rank % m.cols;
-    CHECK(ststhip_stream_synchronize(stream));
-    if (c > 0)
-        m.to_left[s->rank].put(n_planes, send_left, row_bytes, n_rows, stream);
-    if (c + 1 < m.cols)
-        m.to_right[s->rank].put(n_planes, send_right, row_bytes, n_rows, stream);
-    if (c > 0)
-        m.to_right[s->rank - 1].take(n_planes, recv_left, row_bytes, n_rows, stream);
-    if (c + 1 < m.cols)
-        m.to_left[s->rank + 1].take(n_planes, recv_right, row_bytes, n_rows, stream);
-    return STSTHIP_OK;
 }
 
 // one rank of one mesh: both functions, its cells into the assembled results

@@ -89,7 +89,7 @@ def test_strip_update_template_with_user_functors(tmp_path, ranks):
 def test_block_update_template_with_user_functors():
     """tests/cpp/block_template_test.hip: stencil::hip::BlockUpdate -- USER transition functions (time-dependent values,
     sub-iterations and the cells' own coordinates on AoS cells; a two-field cell on per-field planes) on meshes of 1 x 1,
-    2 x 2, 1 x 3 and 3 x 1 blocks (threads of one process on cuda:0, ghost columns and rows through an in-process mailbox):
+    2 x 2, 1 x 3 and 3 x 1 blocks (threads of one process on cuda:0, ghost columns and rows through the in-process mailbox of tests/cpp/mesh_harness.hpp, whose waits are bounded):
     every mesh's assembled cells equal hip::StencilUpdate on the whole grid, bit for bit."""
     binary = os.path.join(OUT, "block_template_test")
     if not os.path.exists(binary):
