@@ -335,6 +335,79 @@ int ststhip_grid_fill(int n, const ststhip_grid_fill_desc *fills, ststhip_stream
 int ststhip_grid_download(int n, const ststhip_grid_copy_desc *copies, ststhip_stream stream);
 int ststhip_grid_upload(int n, const ststhip_grid_copy_desc *copies, ststhip_stream stream);
 
+/* Grid algebra: linear combinations of a few grids and the 2:1 transfer between a fine and a coarse grid, computed
+ * where the cells are (an extension, as the norms and the regions; additive within ABI 6).  What turns a smoother into
+ * a solver between two update calls: a weighted correction u <- (1-w) u + w J(u), a residual, a multigrid cycle
+ * u <- u + P(e).  Views are ststhip_grid_view, elements are STSTHIP_F32 or STSTHIP_F64: planes and members of AoS
+ * cells alike.
+ *
+ * The results are DEFINED OPERATION BY OPERATION: every multiplication and every addition below is done in the
+ * element's own type, rounded once, evaluated left to right and never fused (the library is built with
+ * -ffp-contract=off), so numpy in the same dtype is a bit-exact model.  Subnormal results are kept, not flushed.
+ *
+ * ststhip_grid_combine, element by element over the n_rows x n_cols rectangle: x_k is the element of term k's view at
+ * (term[k].row + i, term[k].col + j), the result lands in the destination at (dst_row + i, dst_col + j):
+ *     acc = coef_0 * x_0;  then for k = 1 .. n_terms-1:  acc = acc + coef_k * x_k.
+ * Coefficients are converted from double to the element's type once, on the host.  (A constant offset: ststhip_grid_fill,
+ * then a combine.)
+ *
+ * ststhip_grid_resample: grids are cell-centred, H x W cells with a halo outside; n_rows and n_cols count COARSE cells
+ * in both modes.
+ *   STSTHIP_RESTRICT_MEAN: the destination is coarse; with s(a, b) = source cell (src_row + a, src_col + b)
+ *     dst(dst_row+i, dst_col+j) = ((s(2i,2j) + s(2i,2j+1)) + (s(2i+1,2j) + s(2i+1,2j+1))) * 0.25
+ *   in exactly this order.  The 2 n_rows x 2 n_cols source rectangle lies inside its view; src_row / src_col may be odd.
+ *   STSTHIP_PROLONG_BILINEAR: the destination is fine; for coarse cell (i, j) of the rectangle and a, b in {0, 1} the
+ *   fine cell (dst_row + 2i + a, dst_col + 2j + b) gets
+ *     h(r) = 0.75 * c(r, j) + 0.25 * c(r, j_far)      j_far = j - 1 for b = 0, j + 1 for b = 1
+ *     v    = 0.75 * h(i)    + 0.25 * h(i_far)         i_far = i - 1 for a = 0, i + 1 for a = 1
+ *   where c(r, q) is source cell (src_row + r, src_col + q), every product and every sum rounded once.  A neighbour
+ *   outside the source VIEW reads `halo`, converted to the element's type (the meaning of Params::halo_value); one
+ *   outside the rectangle but inside the view reads the view, so that tiles and strips compose.
+ *
+ * As for the regions: one to eight entries per call, run in NO particular order and not checked against each other;
+ * nothing is clipped; an empty rectangle (n_rows == 0 or n_cols == 0) succeeds on the host, also with null bases and
+ * without a device; n_rows, n_cols and the byte extent of a rectangle's row in every view are below 2^31 (for a
+ * resample the fine side counts).  Unlike the regions, and as for the norms, base and stride are multiples of the
+ * element's size.  Calls are ordered on `stream` and do not synchronise.
+ *
+ * Overlap.  A term of a combine whose byte span (first byte of its rectangle's first element to the last byte of the
+ * last) intersects the destination's is accepted in two cases only: the term IS the destination (same first-element
+ * address, stride and pitch; a lane reads its own element before it writes it), or it is another member of the same
+ * cells by the regions' rule (same stride and pitch, first elements d bytes apart with elem_size <= d and
+ * d + elem_size <= stride).  A resample refuses any intersection of the destination's span with the span of what it
+ * reads (for a prolongation the neighbours inside the view included).
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID, ststhip_last_error() starts with
+ * "grid algebra"): n outside 1..8, n_terms outside 1..4, an unknown type or mode, stride 0, pitch < width, a null base
+ * with a non-empty rectangle, misalignment, extents that describe more than 2^63 bytes, a rectangle outside its view,
+ * the limits and the overlap rules above. */
+#define STSTHIP_RESTRICT_MEAN 0u
+#define STSTHIP_PROLONG_BILINEAR 1u
+typedef struct {
+    ststhip_grid_view src;
+    uint64_t row, col;               /* where element (0, 0) of the rectangle is read */
+    double coef;
+} ststhip_grid_term;
+typedef struct {
+    ststhip_grid_view dst;
+    uint32_t type;                   /* STSTHIP_F32 or STSTHIP_F64            */
+    uint32_t n_terms;                /* 1 .. 4                                */
+    uint64_t dst_row, dst_col;       /* where element (0, 0) of the rectangle lands */
+    uint64_t n_rows, n_cols;
+    ststhip_grid_term term[4];
+} ststhip_grid_combine_desc;
+typedef struct {
+    ststhip_grid_view dst, src;
+    uint32_t type;                   /* STSTHIP_F32 or STSTHIP_F64            */
+    uint32_t mode;                   /* STSTHIP_RESTRICT_MEAN or STSTHIP_PROLONG_BILINEAR */
+    uint64_t dst_row, dst_col;       /* the first cell written                */
+    uint64_t src_row, src_col;       /* the first cell of the source rectangle */
+    uint64_t n_rows, n_cols;         /* COARSE cells per axis, in both modes  */
+    double halo;                     /* prolong: what a neighbour outside the source view reads */
+} ststhip_grid_resample_desc;
+int ststhip_grid_combine(int n, const ststhip_grid_combine_desc *combines, ststhip_stream stream);
+int ststhip_grid_resample(int n, const ststhip_grid_resample_desc *resamples, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

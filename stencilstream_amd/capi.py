@@ -200,6 +200,30 @@ class GridFillDesc(C.Structure):
                 ("dst_col", C.c_uint64), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("value", C.c_void_p)]
 
 
+class GridTerm(C.Structure):
+    """ststhip_grid_term"""
+
+    _fields_ = [("src", GridView), ("row", C.c_uint64), ("col", C.c_uint64), ("coef", C.c_double)]
+
+
+class GridCombineDesc(C.Structure):
+    """ststhip_grid_combine_desc"""
+
+    _fields_ = [("dst", GridView), ("type", C.c_uint32), ("n_terms", C.c_uint32), ("dst_row", C.c_uint64),
+                ("dst_col", C.c_uint64), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("term", GridTerm * 4)]
+
+
+class GridResampleDesc(C.Structure):
+    """ststhip_grid_resample_desc"""
+
+    _fields_ = [("dst", GridView), ("src", GridView), ("type", C.c_uint32), ("mode", C.c_uint32),
+                ("dst_row", C.c_uint64), ("dst_col", C.c_uint64), ("src_row", C.c_uint64), ("src_col", C.c_uint64),
+                ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("halo", C.c_double)]
+
+
+RESTRICT_MEAN, PROLONG_BILINEAR = 0, 1  # STSTHIP_RESTRICT_MEAN, STSTHIP_PROLONG_BILINEAR
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -292,6 +316,8 @@ def load():
         "ststhip_grid_fill": [C.c_int, C.POINTER(GridFillDesc), vp],
         "ststhip_grid_download": [C.c_int, C.POINTER(GridCopyDesc), vp],
         "ststhip_grid_upload": [C.c_int, C.POINTER(GridCopyDesc), vp],
+        "ststhip_grid_combine": [C.c_int, C.POINTER(GridCombineDesc), vp],
+        "ststhip_grid_resample": [C.c_int, C.POINTER(GridResampleDesc), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -727,6 +753,45 @@ def grid_upload(copies, stream=0):
     """ststhip_grid_upload: the source views are host memory (stride = elem_size, steps 1, any pitch); the host
     memory may be reused when the call returns."""
     _grid_region_call("ststhip_grid_upload", GridCopyDesc, copies, stream)
+
+
+def _algebra_type(dtype):
+    kind = {"f4": 0, "<f4": 0, "float32": 0, "f8": 1, "<f8": 1, "float64": 1}.get(str(dtype))
+    if kind is None:
+        raise ValueError(f"the grid algebra computes with <f4 and <f8 elements, not {dtype}")
+    return kind
+
+
+def grid_combine_desc(dst, dtype, terms, n_rows, n_cols, dst_at=(0, 0)):
+    """A ststhip_grid_combine_desc: over the n_rows x n_cols rectangle of view `dst` from dst_at on,
+    acc = coef_0 * x_0, then acc = acc + coef_k * x_k, in `dtype` ('<f4' / '<f8').  `terms`: one to four
+    (coef, view) or (coef, view, (row, col)); (row, col) is where element (0, 0) of the rectangle is read."""
+    terms = list(terms)
+    desc = GridCombineDesc(dst, _algebra_type(dtype), len(terms), int(dst_at[0]), int(dst_at[1]), int(n_rows),
+                           int(n_cols))
+    for k, term in enumerate(terms[:4]):  # (a fifth term: n_terms says so, and the library refuses it)
+        coef, src = term[0], term[1]
+        row, col = term[2] if len(term) > 2 else (0, 0)
+        desc.term[k] = GridTerm(src, int(row), int(col), float(coef))
+    return desc
+
+
+def grid_resample_desc(dst, src, dtype, mode, n_rows, n_cols, dst_at=(0, 0), src_at=(0, 0), halo=0.0):
+    """A ststhip_grid_resample_desc: mode RESTRICT_MEAN (`dst` is coarse) or PROLONG_BILINEAR (`dst` is fine); n_rows,
+    n_cols count coarse cells in both; `halo` is what a prolongation reads outside the source view."""
+    return GridResampleDesc(dst, src, _algebra_type(dtype), int(mode), int(dst_at[0]), int(dst_at[1]), int(src_at[0]),
+                            int(src_at[1]), int(n_rows), int(n_cols), float(halo))
+
+
+def grid_combine(combines, stream=0):
+    """ststhip_grid_combine: 1..8 grid_combine_desc() entries, queued on `stream`; does not synchronise.  The entries
+    run in no particular order."""
+    _grid_region_call("ststhip_grid_combine", GridCombineDesc, combines, stream)
+
+
+def grid_resample(resamples, stream=0):
+    """ststhip_grid_resample: 1..8 grid_resample_desc() entries, queued on `stream`; does not synchronise."""
+    _grid_region_call("ststhip_grid_resample", GridResampleDesc, resamples, stream)
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

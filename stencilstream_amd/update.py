@@ -262,6 +262,68 @@ class Grid:
                                                     n_cols, dst_at=(a0, a1), src_at=(r0, c0), step=(sr, sc))],
                                torch_stream.cuda_stream)
 
+    # ---- computing with grids where the cells are (ststhip_grid_combine / ststhip_grid_resample) ----
+    def _float_element(self, field):
+        """(dtype, byte offset in the cell) of the float a grid-algebra call computes with: the member `field`, or the
+        cell itself where cells are plain floats."""
+        kind, offset = self._element(field)
+        if kind.str not in ("<f4", "<f8"):
+            what = "the cells are" if field is None else f"field {field!r} is"
+            raise ValueError(f"{what} {kind}: the grid algebra computes with <f4 and <f8 elements")
+        return kind, offset
+
+    def combine(self, terms, field=None, rows=None, cols=None):
+        """this[field] = coef_0 * x_0 (+ coef_1 * x_1 ...) over rows[0]:rows[1], cols[0]:cols[1] (None = the whole
+        axis).  `terms`: one to four (coef, grid) or (coef, grid, field) of grids of this grid's extent (any cell type)
+        whose element has this element's dtype; the same rectangle applies to all.  Every product and every sum is
+        rounded once in that dtype, left to right, so numpy in the same dtype gives the same bits.  A term may be this
+        grid's own element (in place) or another member of its cells.  Queued; does not wait."""
+        kind, offset = self._float_element(field)
+        terms = [tuple(t) for t in terms]
+        if not 1 <= len(terms) <= 4:
+            raise ValueError("a combine takes 1 to 4 terms")
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        sources = []
+        for term in terms:
+            if len(term) not in (2, 3):
+                raise ValueError("a term is (coef, grid) or (coef, grid, field)")
+            grid, its_field = term[1], (term[2] if len(term) == 3 else None)
+            if (grid.height, grid.width) != (self.height, self.width):
+                raise ValueError("a term's grid has not the same size as the grid")
+            its_kind, its_offset = grid._float_element(its_field)
+            if its_kind != kind:
+                raise ValueError(f"a term's element is {its_kind}, the destination's {kind}")
+            sources.append((float(term[0]), grid, its_offset))
+        if r1 > r0 and c1 > c0:
+            with self._on_device() as torch_stream:
+                table = [(coef, grid._view(its_offset), (r0, c0)) for coef, grid, its_offset in sources]
+                capi.grid_combine([capi.grid_combine_desc(self._view(offset), kind.str, table, r1 - r0, c1 - c0,
+                                                          dst_at=(r0, c0))], torch_stream.cuda_stream)
+
+    def _transfer(self, other, mode, coarse, fine, field, src_field, halo):
+        kind, offset = self._float_element(field)
+        its_kind, its_offset = other._float_element(src_field)
+        if its_kind != kind:
+            raise ValueError(f"the source's element is {its_kind}, the destination's {kind}")
+        if (fine.height, fine.width) != (2 * coarse.height, 2 * coarse.width):
+            raise ValueError(f"the fine grid ({fine.height} x {fine.width}) has not twice the extents of the coarse "
+                             f"one ({coarse.height} x {coarse.width})")
+        if coarse.height and coarse.width:
+            with self._on_device() as torch_stream:
+                capi.grid_resample([capi.grid_resample_desc(self._view(offset), other._view(its_offset), kind.str, mode,
+                                                            coarse.height, coarse.width, halo=halo)],
+                                   torch_stream.cuda_stream)
+
+    def restrict_from(self, fine, field=None, src_field=None):
+        """This (coarse) grid's element becomes the mean of the 2 x 2 cells of `fine`, whose extents are twice this
+        grid's: ((s(2i,2j) + s(2i,2j+1)) + (s(2i+1,2j) + s(2i+1,2j+1))) * 0.25, one rounding each.  Queued."""
+        self._transfer(fine, capi.RESTRICT_MEAN, self, fine, field, src_field, 0.0)
+
+    def prolong_from(self, coarse, halo=0.0, field=None, src_field=None):
+        """This (fine) grid's element becomes the cell-centred bilinear interpolation (weights 0.75 / 0.25 per axis) of
+        `coarse`, whose extents are half this grid's; a neighbour outside the coarse grid reads `halo`.  Queued."""
+        self._transfer(coarse, capi.PROLONG_BILINEAR, coarse, self, field, src_field, float(halo))
+
 
 @dataclass
 class Params:
