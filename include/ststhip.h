@@ -408,6 +408,61 @@ typedef struct {
 int ststhip_grid_combine(int n, const ststhip_grid_combine_desc *combines, ststhip_stream stream);
 int ststhip_grid_resample(int n, const ststhip_grid_resample_desc *resamples, ststhip_stream stream);
 
+/* Grid stencils: a 3 x 3 linear operator applied to a grid once, with an optional right-hand side (an extension, as
+ * the algebra; additive within ABI 6).  The piece of the routes above that reads neighbours: a residual r = f - A u is
+ * weight = -A, rhs_coef = 1; a Poisson relaxation u <- 1/4 (N + W + E + S) + 1/4 h^2 f is
+ * weight = {0, 1/4, 0,  1/4, 0, 1/4,  0, 1/4, 0}, rhs_coef = 1/4 h^2.  Views and element types are the algebra's.
+ *
+ * The result is DEFINED OPERATION BY OPERATION, as the algebra's.  For element (i, j) of the n_rows x n_cols rectangle
+ * let s(a, b) be source cell (src_row + i + a, src_col + j + b).  The taps of the shape are taken in row-major order,
+ *     BOX9:   (-1,-1) (-1,0) (-1,+1) (0,-1) (0,0) (0,+1) (+1,-1) (+1,0) (+1,+1)
+ *     CROSS5: (-1,0) (0,-1) (0,0) (0,+1) (+1,0)
+ * and with w(a, b) = weight[3 * (a + 1) + (b + 1)]
+ *     acc = w_first * s_first;   then, for every further tap in that order:   acc = acc + w_k * s_k;
+ *     if has_rhs:                acc = acc + rhs_coef * rhs(rhs_row + i, rhs_col + j);
+ *     dst(dst_row + i, dst_col + j) = acc
+ * Every product and every sum is rounded once in the element's type and never fused; subnormals are kept.  Weights,
+ * rhs_coef and halo are converted from double once, on the host.  EVERY tap of the shape is multiplied, also one whose
+ * weight is zero: 0 * inf is NaN, as in numpy.  The four corner taps of CROSS5 are neither read nor multiplied; a
+ * CROSS5 entry whose corner weights are not +0.0 or -0.0 is refused.  A neighbour outside the source VIEW reads `halo`
+ * (the meaning of Params::halo_value); one outside the rectangle but inside the view reads the view, so that tiles and
+ * strips compose, as for STSTHIP_PROLONG_BILINEAR.
+ *
+ * The conventions are the algebra's: one to eight entries per call, run in NO particular order and not checked against
+ * each other; nothing is clipped; an empty rectangle succeeds on the host, also with null bases and without a device;
+ * n_rows, n_cols and the byte extent of a rectangle's row in every view are below 2^31; bases and strides are
+ * multiples of the element's size; the call is ordered on `stream` and does not synchronise.
+ *
+ * Overlap.  What the stencil reads is the rectangle widened by one cell on every side where that lies inside the view.
+ * The byte span of that may intersect the destination's span in one case only: src is another member of the
+ * destination's cells by the regions' rule (same stride and pitch, the first elements of the two rectangles d bytes
+ * apart with elem_size <= d and d + elem_size <= stride); a lane then never writes bytes that another lane reads.  src
+ * being the destination itself is refused: a stencil in place is a race.  rhs follows the rule of a combine's term: it
+ * may BE the destination (same first-element address, stride and pitch; a lane reads its own element before it writes
+ * it) or another member of the same cells; every other intersection is refused.
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID, ststhip_last_error() starts with
+ * "grid stencil"): n outside 1..8, an unknown type or shape, reserved != 0, stride 0, pitch < width, a null base with a
+ * non-empty rectangle, misalignment, extents that describe more than 2^63 bytes, a rectangle outside its view, a weight
+ * or (with has_rhs) an rhs_coef that is not finite (a halo may be anything), non-zero corner weights with CROSS5, the
+ * limits and the overlap rules above.  With has_rhs == 0, rhs, rhs_row, rhs_col and rhs_coef are ignored. */
+#define STSTHIP_STENCIL_CROSS5 0u     /* taps N, W, C, E, S                    */
+#define STSTHIP_STENCIL_BOX9 1u       /* all nine taps                         */
+typedef struct {
+    ststhip_grid_view dst, src, rhs; /* rhs is ignored (may be all zero) when has_rhs == 0 */
+    uint32_t type;                   /* STSTHIP_F32 or STSTHIP_F64            */
+    uint32_t shape;                  /* STSTHIP_STENCIL_CROSS5 or STSTHIP_STENCIL_BOX9 */
+    uint32_t has_rhs, reserved;      /* reserved = 0                          */
+    uint64_t dst_row, dst_col;       /* where element (0, 0) of the rectangle lands */
+    uint64_t src_row, src_col;       /* the centre tap of element (0, 0)      */
+    uint64_t rhs_row, rhs_col;       /* where element (0, 0) of the right-hand side is read */
+    uint64_t n_rows, n_cols;
+    double weight[9];                /* row-major: weight[3*(a+1) + (b+1)] multiplies src(i+a, j+b) */
+    double rhs_coef;
+    double halo;                     /* what a neighbour outside the source view reads */
+} ststhip_grid_stencil_desc;
+int ststhip_grid_stencil(int n, const ststhip_grid_stencil_desc *stencils, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

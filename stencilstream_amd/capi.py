@@ -224,6 +224,19 @@ class GridResampleDesc(C.Structure):
 RESTRICT_MEAN, PROLONG_BILINEAR = 0, 1  # STSTHIP_RESTRICT_MEAN, STSTHIP_PROLONG_BILINEAR
 
 
+class GridStencilDesc(C.Structure):
+    """ststhip_grid_stencil_desc"""
+
+    _fields_ = [("dst", GridView), ("src", GridView), ("rhs", GridView), ("type", C.c_uint32), ("shape", C.c_uint32),
+                ("has_rhs", C.c_uint32), ("reserved", C.c_uint32), ("dst_row", C.c_uint64), ("dst_col", C.c_uint64),
+                ("src_row", C.c_uint64), ("src_col", C.c_uint64), ("rhs_row", C.c_uint64), ("rhs_col", C.c_uint64),
+                ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("weight", C.c_double * 9), ("rhs_coef", C.c_double),
+                ("halo", C.c_double)]
+
+
+STENCIL_CROSS5, STENCIL_BOX9 = 0, 1  # STSTHIP_STENCIL_CROSS5, STSTHIP_STENCIL_BOX9
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -318,6 +331,7 @@ def load():
         "ststhip_grid_upload": [C.c_int, C.POINTER(GridCopyDesc), vp],
         "ststhip_grid_combine": [C.c_int, C.POINTER(GridCombineDesc), vp],
         "ststhip_grid_resample": [C.c_int, C.POINTER(GridResampleDesc), vp],
+        "ststhip_grid_stencil": [C.c_int, C.POINTER(GridStencilDesc), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -792,6 +806,30 @@ def grid_combine(combines, stream=0):
 def grid_resample(resamples, stream=0):
     """ststhip_grid_resample: 1..8 grid_resample_desc() entries, queued on `stream`; does not synchronise."""
     _grid_region_call("ststhip_grid_resample", GridResampleDesc, resamples, stream)
+
+
+def grid_stencil_desc(dst, src, dtype, shape, weights, n_rows, n_cols, dst_at=(0, 0), src_at=(0, 0), halo=0.0, rhs=None,
+                      rhs_coef=1.0, rhs_at=(0, 0)):
+    """A ststhip_grid_stencil_desc: over the n_rows x n_cols rectangle, acc = w_first * s_first, then
+    acc = acc + w_k * s_k over the taps of `shape` (STENCIL_BOX9 / STENCIL_CROSS5) in row-major order, then
+    acc = acc + rhs_coef * rhs where a view `rhs` is given, in `dtype` ('<f4' / '<f8').  `weights`: nine numbers,
+    row-major (3 x 3 nested or flat); weights[3 * (a + 1) + (b + 1)] multiplies src(i + a, j + b).  `halo` is what a
+    neighbour outside the view `src` reads."""
+    flat = [float(w) for row in weights for w in (row if hasattr(row, "__len__") else [row])]
+    if len(flat) != 9:
+        raise ValueError(f"a grid stencil has nine weights, not {len(flat)}")
+    desc = GridStencilDesc(dst, src, GridView() if rhs is None else rhs, _algebra_type(dtype), int(shape),
+                           0 if rhs is None else 1, 0, int(dst_at[0]), int(dst_at[1]), int(src_at[0]), int(src_at[1]),
+                           int(rhs_at[0]), int(rhs_at[1]), int(n_rows), int(n_cols))
+    desc.weight[:] = flat
+    desc.rhs_coef, desc.halo = float(rhs_coef), float(halo)
+    return desc
+
+
+def grid_stencil(stencils, stream=0):
+    """ststhip_grid_stencil: 1..8 grid_stencil_desc() entries, queued on `stream`; does not synchronise.  The entries
+    run in no particular order."""
+    _grid_region_call("ststhip_grid_stencil", GridStencilDesc, stencils, stream)
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

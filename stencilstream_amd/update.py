@@ -324,6 +324,61 @@ class Grid:
         `coarse`, whose extents are half this grid's; a neighbour outside the coarse grid reads `halo`.  Queued."""
         self._transfer(coarse, capi.PROLONG_BILINEAR, coarse, self, field, src_field, float(halo))
 
+    # ---- a 3 x 3 linear operator applied once (ststhip_grid_stencil) ----
+    def apply_stencil(self, src, *, box=None, cross=None, halo=0.0, rhs=None, rhs_coef=1.0, field=None, src_field=None,
+                      rhs_field=None, rows=None, cols=None):
+        """this[field] = sum of w(a, b) * src[src_field](i + a, j + b) (+ rhs_coef * rhs[rhs_field](i, j)) over
+        rows[0]:rows[1], cols[0]:cols[1] (None = the whole axis); the same rectangle applies to all three grids, which
+        have this grid's extents (any cell type) and elements of this element's dtype.  Exactly one of `box` (3 x 3
+        weights, row-major: all nine taps, also those whose weight is zero) and `cross` ((n, w, c, e, s): five taps,
+        the corners are not read) is given; the shape is never inferred from zeros.  The taps are taken in row-major
+        order, acc = w_first * s_first, then acc = acc + w_k * s_k, then the right-hand side: every product and every
+        sum is rounded once in that dtype, so numpy in the same dtype gives the same bits.  A neighbour outside the
+        GRID reads `halo`, one outside the rectangle reads the grid.  `src` may be another member of this grid's cells
+        but not the destination itself; `rhs` may be either.  A residual r = f - A u: weights -A, rhs=f; a relaxation
+        with a source: cross=(.25, .25, 0, .25, .25), rhs=f, rhs_coef=h*h/4.  Queued; does not wait."""
+        kind, offset = self._float_element(field)
+        if (box is None) == (cross is None):
+            raise ValueError("a stencil is given as box= (3 x 3 weights) or as cross= (n, w, c, e, s), one of the two")
+        if box is not None:
+            weights = np.asarray(box, dtype=np.float64)
+            if weights.shape != (3, 3):
+                raise ValueError(f"box= takes 3 x 3 weights, not an array of shape {weights.shape}")
+            shape, weights = capi.STENCIL_BOX9, [float(w) for w in weights.reshape(-1)]
+        else:
+            taps = np.asarray(cross, dtype=np.float64)
+            if taps.shape != (5,):
+                raise ValueError(f"cross= takes five weights (n, w, c, e, s), not an array of shape {taps.shape}")
+            n, w, c, e, s = (float(t) for t in taps)
+            shape, weights = capi.STENCIL_CROSS5, [0.0, n, 0.0, w, c, e, 0.0, s, 0.0]
+        if not np.all(np.isfinite(weights)):
+            raise ValueError("a weight of the stencil is not finite")
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        others = [("the source", src, src_field)]
+        if rhs is not None:
+            others.append(("the right-hand side", rhs, rhs_field))
+            if not np.isfinite(float(rhs_coef)):
+                raise ValueError("rhs_coef is not finite")
+        elif rhs_field is not None:
+            raise ValueError("rhs_field names a member of a right-hand side that is not given")
+        views = []
+        for what, grid, its_field in others:
+            if (grid.height, grid.width) != (self.height, self.width):
+                raise ValueError(f"{what}'s grid has not the same size as the grid")
+            its_kind, its_offset = grid._float_element(its_field)
+            if its_kind != kind:
+                raise ValueError(f"{what}'s element is {its_kind}, the destination's {kind}")
+            views.append((grid, its_offset))
+        if views[0][0].cells.data_ptr() == self.cells.data_ptr() and views[0][1] == offset:
+            raise ValueError("the source is the destination itself: a stencil in place is a race")
+        if r1 > r0 and c1 > c0:
+            with self._on_device() as torch_stream:
+                f = None if rhs is None else views[1][0]._view(views[1][1])
+                capi.grid_stencil([capi.grid_stencil_desc(self._view(offset), views[0][0]._view(views[0][1]), kind.str,
+                                                          shape, weights, r1 - r0, c1 - c0, (r0, c0), (r0, c0),
+                                                          float(halo), f, float(rhs_coef), (r0, c0))],
+                                  torch_stream.cuda_stream)
+
 
 @dataclass
 class Params:
