@@ -50,7 +50,19 @@ template <JacobiVariant V> struct Jacobi : public BaseTransitionFunction {
         } else if constexpr (V == JacobiVariant::General4) {
             return coef[0] * n + coef[1] * w + coef[2] * so + coef[3] * e;
         } else if constexpr (V == JacobiVariant::General5) {
+#ifdef STSTHIP_FMA_FLAVOUR
+            // The flavour built with fused multiply-adds ("jacobi5general_fma").  With -ffp-contract=fast the compiler
+            // picks per kernel instantiation WHICH product of c0*N + c1*W it fuses, so the check-free code, the edge
+            // code and the stages of one launch rounded differently and a result depended on the launch's chunk plan
+            // (up to 3 ulp, tests/test_launch_geometry_gpu.py).  The fusion is spelled out instead, in the order gcc
+            // gives the oracle's fused build (oracle/Makefile, liboracle_fma.so): the first product of the sum is fused
+            // into the first addition, every later product into its own.  One multiplication and four fused
+            // multiply-adds, as before.
+            return __builtin_fmaf(coef[4], c, __builtin_fmaf(coef[3], e, __builtin_fmaf(coef[2], so,
+                                  __builtin_fmaf(coef[0], n, coef[1] * w))));
+#else
             return coef[0] * n + coef[1] * w + coef[2] * so + coef[3] * e + coef[4] * c;
+#endif
         } else {
             float sum = 0.0f;
 #pragma unroll

@@ -17,6 +17,18 @@ def test_host_api():
     assert b"0 failures" in res.stdout
 
 
+def test_launch_plan_on_the_host():
+    """tests/cpp/launch_plan_test.hip: the chunk and tier planners of a sweep launch against the kernel's decode of
+    blockIdx, over tapers of up to three entries, chunk lengths, launch concurrencies and both dispatch orders: every
+    row of the launch is produced by exactly one unit.  Opens no GPU."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), os.path.join(OUT, "launch_plan_test")])
+    res = subprocess.run([os.path.join(OUT, "launch_plan_test")], capture_output=True, timeout=600)
+    assert res.returncode == 0, res.stdout.decode() + res.stderr.decode()
+    assert b" 0 failures" in res.stdout
+    cases = int(res.stdout.split(b"launch plan: ")[1].split()[0])
+    assert cases >= 804000, cases  # the planner model this test was specified from covered that many
+
+
 @pytest.mark.gpu
 def test_hip_api():
     binary = os.path.join(OUT, "hip_api_test")

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from sweep_workloads import fdtd_setup  # noqa: F401 -- other test files import it from here
 
 pytestmark = pytest.mark.gpu
 
@@ -164,30 +165,6 @@ def test_selfcheck_known_answer(gpu, oracle, case, name, radius, split):
     assert (out["r"] == np.arange(H)[:, None]).all() and (out["c"] == np.arange(W)[None, :]).all()
     assert (out["i_iteration"] == offset + n).all() and (out["i_subiteration"] == 0).all()
     assert np.array_equal(bits(out), bits(oracle.selfcheck(radius, oracle.selfcheck_input(H, W, offset), offset, n)))
-
-
-def fdtd_setup(oracle, H, W):
-    from stencilstream_amd import capi
-
-    # parameters in the range of examples/fdtd/experiments/default.json, source off-centre
-    kw = dict(dt=8.3e-18, t_0=3e-13 * 0.01, tau=1e-13 * 0.01, omega=7.5e14, cutoff_iteration=40,
-              detect_iteration=10, source_radius_squared=36.0, source_r=H / 2.0 + 3, source_c=W / 2.0 - 2,
-              source_distance_bound=0.0, double_center_rc=float(H))
-    kw["source_distance_bound"] = 36.0 - (kw["source_c"] ** 2 + kw["source_r"] ** 2)
-    po, pc = oracle.FdtdParams(), capi.FdtdParams()
-    for k, v in kw.items():
-        setattr(po, k, v)
-        setattr(pc, k, v)
-    rng = np.random.default_rng(3)
-    cells = np.zeros((H, W), dtype=oracle.FDTD_CELL)
-    for f in ("ex", "ey", "hz"):
-        cells[f] = (rng.random((H, W), dtype=np.float32) - 0.5) * 1e-3
-    inside = ((np.arange(H)[:, None] - H / 2) ** 2 + (np.arange(W)[None, :] - W / 2) ** 2) < (min(H, W) * 0.4) ** 2
-    cells["ca"] = np.where(inside, 1.0, 1.0).astype(np.float32)
-    cells["cb"] = np.where(inside, 0.31, 0.0).astype(np.float32)
-    cells["da"] = np.where(inside, 1.0, 1.0).astype(np.float32)
-    cells["db"] = np.where(inside, 0.29, 0.0).astype(np.float32)
-    return po, pc, cells
 
 
 @pytest.mark.parametrize("layout", ["grouped", "planes", "aos"])

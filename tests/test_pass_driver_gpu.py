@@ -18,11 +18,11 @@ import numpy as np
 import pytest
 
 from pass_schedule import Launch, assert_launch_state_idle, check_schedule, check_tile_frontiers, halvings
+from sweep_workloads import Workload
 
 pytestmark = pytest.mark.gpu
 
 BIG = (2048, 1024)          # the smallest grid the existing tests run in two and three strips and in eight blocks
-N_THREADS = 8
 _keys = itertools.count(0x7E57_0001)   # a fresh tune_key per probing case: nothing depends on the order of the tests
 
 
@@ -34,84 +34,7 @@ def file_time():
 
 
 # ------------------------------------------------------------------------------------------------ workloads
-class Workload:
-    """A precompiled transition function on one grid: planes on the device, the oracle's cells after n generations."""
-
-    def __init__(self, oracle, app, shape):
-        import torch
-
-        from stencilstream_amd import capi
-
-        self.oracle, self.app, self.shape = oracle, app, shape
-        H, W = shape
-        rng = np.random.default_rng(H * 131 + W + len(app))
-        if app == "jacobi5general":
-            self.coef = [0.11, 0.19, 0.23, 0.31, 0.16]
-            self.params = capi.JacobiParams()
-            for i, c in enumerate(self.coef):
-                self.params.coef[i] = c
-            self.halo = np.float32(0.0).tobytes()
-            self.known = {0: rng.random((H, W), dtype=np.float32)}
-        else:
-            assert app == "hotspot"
-            self.hp = oracle.hotspot_params(H, W)
-            self.params = capi.HotspotParams(self.hp.Rx_1, self.hp.Ry_1, self.hp.Rz_1, self.hp.Cap_1)
-            self.halo = bytes(8)
-            cells = np.zeros((H, W), dtype=oracle.HOTSPOT_CELL)
-            cells["temp"] = 320 + 10 * rng.random((H, W), dtype=np.float32)
-            cells["power"] = rng.random((H, W), dtype=np.float32) * 0.01
-            self.known = {0: cells}
-        self.info = capi.app_info(app)
-        self.dom = capi.Domain(H, W, 0, H, W)
-        self.host = self.planes_of(self.known[0])
-        self.src = [torch.from_numpy(p).cuda() for p in self.host]
-        self.dst = [torch.empty_like(t) for t in self.src]
-        self.stream = torch.cuda.Stream()
-        self._launch_ms = None
-        torch.cuda.synchronize()
-
-    def planes_of(self, cells):
-        if self.app == "jacobi5general":
-            return [np.ascontiguousarray(cells)]
-        return [np.ascontiguousarray(cells["temp"]), np.ascontiguousarray(cells["power"])]
-
-    def want(self, n):
-        """The oracle's planes after n generations (neither function depends on the generation's number: continued
-        from the nearest earlier result, computed once, never changed)."""
-        if n not in self.known:
-            m = max(k for k in self.known if k < n)
-            if self.app == "jacobi5general":
-                self.known[n] = self.oracle.jacobi("Jacobi5General", self.coef, self.known[m], n - m, halo=0.0,
-                                                   n_threads=N_THREADS)
-            else:
-                self.known[n] = self.oracle.hotspot(self.hp, self.known[m], n - m, n_threads=N_THREADS)
-        return self.planes_of(self.known[n])
-
-    def desc(self, alt=0, key=0):
-        from stencilstream_amd import capi
-
-        return capi.sweep_desc_of(self.app, alt, key)
-
-    def launch_ms(self):
-        """One undelayed launch of the deepest depth over the whole grid, between two events (the second of two)."""
-        import torch
-
-        from stencilstream_amd import capi
-
-        if self._launch_ms is None:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            H = self.shape[0]
-            for _ in range(2):
-                t0.record(self.stream)
-                capi.app_sweep(self.app, self.params, self.halo, self.dom, [t.data_ptr() for t in self.src],
-                               [t.data_ptr() for t in self.dst], 0, H, 0, self.info.max_generations,
-                               self.stream.cuda_stream)
-                t1.record(self.stream)
-                t1.synchronize()
-            self._launch_ms = t0.elapsed_time(t1)
-        return self._launch_ms
-
-
+# (the class lives in tests/sweep_workloads.py, shared with the tests of single launches)
 _workloads = {}
 
 

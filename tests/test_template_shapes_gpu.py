@@ -10,7 +10,14 @@ prints the functor, the grid, the generations, the depth and the first differing
 
 The environments: none (small grids take the narrow form where a shape has one); the default shape; the default shape
 with the one-word functor's depth 16 outright (unmeasured launches run 8); the default shape with row chunks of eight
-rows (chunk seams at every height).  STSTHIP_ALLOW_SPILLING_DEPTHS=1 is for binaries whose report names a
+rows (chunk seams at every height); the default shape with row chunks of sixteen rows, a taper of two entries and
+renumbered workgroups (tapered-xcd).  The taper needs tiers of at least four rows that are shorter than the chunk, so
+it engages at the taller heights only.  Of a functor's four heights 1, 3, G + 1 and 4 G + 7 (G = radius x
+sub-iterations x depth) `build/tests/launch_plan_test plan 0 <h> <h> <G>` prints, under that environment: one chunk for
+1 and 3 and for G + 1 up to 16 rows (F3x1 4, D2x1 5, the fat cells and Quad1 9, D1 13); two 16-row chunks in one tier
+for G + 1 = 17 (U16, Mixed2) and 19 (F3); two tiers (16 / 4) for F2x2's G + 1 = 25 and D2x1's 4 G + 7 = 23; one tier
+for F3x1's 4 G + 7 = 19; and three tiers (16 / 8 / 4) for every other 4 G + 7: 39 (Tri1, Quad1, Octo1, Penta1), 55
+(D1), 71 (U16, Mixed2), 79 (F3) and 103 (F2x2).  STSTHIP_ALLOW_SPILLING_DEPTHS=1 is for binaries whose report names a
 spill-free depth below the compiled one (SPILLING below), so that the deep kernels are compared as well: on gfx950
 every case reports its compiled depth as spill-free (U16 16, F3 6, D1 12, the fat cells 8, F2x2 6, F3x1 1, D2x1 2), so
 no binary is listed and the environment is left out; each test asserts the reported depths, and a case that drops
@@ -35,6 +42,7 @@ ENVIRONMENTS = {
     "narrow-form": {},
     "default-shape": WIDE,
     "chunks-of-8-rows": dict(WIDE, STSTHIP_CHUNK_ROWS="8"),
+    "tapered-xcd": dict(WIDE, STSTHIP_CHUNK_ROWS="16", STSTHIP_TAPER="500:2,250:4", STSTHIP_XCD_REMAP="1"),
 }
 # the binary that holds the one-word functor (U16: compiled 16 deep, 8 by default)
 DEPTH_16 = ("shape_test_a", dict(WIDE, STSTHIP_TUNE_DEPTH="16"))
@@ -46,7 +54,8 @@ CASES.append(pytest.param(*DEPTH_16, id=f"{DEPTH_16[0]}-depth-16"))
 CASES += [pytest.param(b, {"STSTHIP_ALLOW_SPILLING_DEPTHS": "1"}, id=f"{b}-spilling-depths") for b in SPILLING]
 
 KNOBS = ("STSTHIP_NARROW_FORM_KCELLS", "STSTHIP_TUNE_DEPTH", "STSTHIP_CHUNK_ROWS", "STSTHIP_ALLOW_SPILLING_DEPTHS",
-         "STSTHIP_MAX_GENERATIONS", "STSTHIP_NARROW_BAND_ROWS")
+         "STSTHIP_MAX_GENERATIONS", "STSTHIP_NARROW_BAND_ROWS", "STSTHIP_TAPER", "STSTHIP_XCD_REMAP",
+         "STSTHIP_LAST_CHUNK_EARLY")
 
 
 def binary(name):
