@@ -586,6 +586,24 @@ struct Sweep {
         else
             return G;
     }();
+    // (what can be told at compile time: the cone grows by a column per generation at the least, and by no more than
+    // the generic depth)
+    static constexpr bool hint_in_range = [] {
+        if constexpr (requires { F::halo_columns_per_generation; })
+            return F::halo_columns_per_generation >= 1 && F::halo_columns_per_generation <= std::size_t(R * NS);
+        else
+            return true;
+    }();
+    static_assert(hint_in_range, "halo_columns_per_generation must lie in [1, stencil_radius * n_subiterations]");
+    // The hint and interior() together: interior() is promised 0 < column < width - 1 for every cell that can reach the
+    // output.  At the generic depth a level-l cell that matters lies l * R columns inside the footprint; under the hint
+    // it need not -- a first sub-step that reads west only is valid up to the footprint's LAST column, and its cells
+    // reach the output (the cone grows by the hint per generation, not per sub-step).  A footprint that ends where
+    // the grid ends would hand interior() the grid's last column, so such a function's check-free units keep one
+    // column away from the grid's east edge (entry(); found by the shape matrix's OneWayRim: the last output column
+    // of the strip whose footprint ended at the edge was wrong).  The west side needs nothing: the footprint starts
+    // at a positive column already.  No other function's kernels change.
+    static constexpr bool hinted_interior = GC < G && requires(F const &f, StencilImpl const &s) { f.interior(s); };
     static constexpr int GX = round_up(GC, K);  // column halo rounded to whole lanes
     static constexpr int LW = wave_size * K;    // columns a wave loads
     static constexpr int OW = LW - 2 * GX;      // columns a unit of the wave grid produces
@@ -1035,9 +1053,10 @@ struct Sweep {
 
         const int xw0 = g.out_col_begin + strip * OW - GX; // footprint of the unit
         // (xw0 > 0, not >= 0: the check-free code tells the transition function that its column is positive; col_lo and
-        // col_hi lie inside the grid; the strip's columns must all be columns to produce)
+        // col_hi lie inside the grid; the strip's columns must all be columns to produce; hinted_interior: see there)
         const bool interior = INTERIOR_VARIANT && xw0 > 0 && xw0 >= g.col_lo && xw0 + LW <= g.col_hi &&
-                              xw0 + LW - GX <= g.out_col_end && ya - G >= 0 && yb + G <= g.grid_h;
+                              xw0 + LW - GX <= g.out_col_end && ya - G >= 0 && yb + G <= g.grid_h &&
+                              (!hinted_interior || xw0 + LW < g.grid_w);
         // the stage of a wave is a compile-time property of the code it runs (levels, iteration and sub-iteration
         // indices, fused forms): one instantiation per stage, selected by the wave's index in the workgroup
         static_for<0, W>([&](auto sg) __attribute__((always_inline)) {

@@ -8,8 +8,9 @@
 // depends on rounding or on the order of operations; nothing calls libm.
 //
 // The file is included by the HIP binaries shape_test_a ... shape_test_d (the cells, the functors, the static asserts
-// on their shapes and the driver) and by the host-only shape_host_test (the cells and the functors alone, checked
-// against a plain double loop).
+// on their shapes and the driver), through hook_cases.hpp by shape_test_e ... shape_test_j (functors with the hooks,
+// hints, tunings and states a transition function may add) and by the host-only shape_host_test (the cells and the
+// functors alone, checked against a plain double loop).
 #pragma once
 #include "mini_test.hpp"
 #include <StencilStream/Stencil.hpp>
@@ -128,8 +129,20 @@ struct Context {
     u32 row, column, height, width, iteration, subiteration, tdv;
 };
 
+// ------------------------------------------------------------------ what a sub-iteration reads
+// Field f of the neighbour at offset o (row-major in the D x D neighbourhood) is read in sub-iteration (o + f) mod NS --
+// every sub-iteration reads other fields and other neighbours, a generation reads them all; the centre cell is read
+// whole every time.  No field is merely copied.
+struct RotatingReads {
+    template <int D, int NS> static constexpr bool reads(int o, int f, u32 subiteration) {
+        return NS == 1 || o == (D * D) / 2 || u32(o + f) % u32(NS) == subiteration;
+    }
+    static constexpr bool copied(int) { return false; }
+};
+
 // ------------------------------------------------------------------ the functor
-template <typename CellT, std::size_t R, std::size_t NS, typename TDVT = std::monostate> struct Hash {
+template <typename CellT, std::size_t R, std::size_t NS, typename TDVT = std::monostate, typename Reads = RotatingReads>
+struct Hash {
     using Cell = CellT;
     using TimeDependentValue = TDVT;
     static constexpr std::size_t stencil_radius = R;
@@ -148,11 +161,8 @@ template <typename CellT, std::size_t R, std::size_t NS, typename TDVT = std::mo
             return TDVT{};
     }
 
-    // Field f of the neighbour at offset o is read in sub-iteration (o + f) mod NS -- every sub-iteration reads other
-    // fields and other neighbours, a generation reads them all; the centre cell is read whole every time.
-    static constexpr bool reads(int o, int f, u32 subiteration) {
-        return NS == 1 || o == (D * D) / 2 || u32(o + f) % u32(NS) == subiteration;
-    }
+    // what a sub-iteration reads is a policy (RotatingReads above; hook_cases.hpp has one-way ones)
+    static constexpr bool reads(int o, int f, u32 subiteration) { return Reads::template reads<D, int(NS)>(o, f, subiteration); }
 
     // `at(dr, dc)`: the neighbour dr rows south and dc columns east of the cell
     template <typename Neighbour> Cell evaluate(Context const &c, Neighbour &&at) const {
@@ -165,7 +175,13 @@ template <typename CellT, std::size_t R, std::size_t NS, typename TDVT = std::mo
                     hash += to_word(field<f>(neighbour)) * odd(u32(o) * 8u + u32(f));
             });
         });
-        return cell_from<CellT>(finalize(hash));
+        CellT result = cell_from<CellT>(finalize(hash));
+        // fields the policy says are only copied keep the centre cell's value
+        stencil::internal::static_for<0, NF>([&](auto f) {
+            if constexpr (Reads::copied(int(f)))
+                field<f>(result) = field<f>(at(0, 0));
+        });
+        return result;
     }
 
     Cell operator()(stencil::Stencil<CellT, R, TDVT> const &s) const {
@@ -260,15 +276,17 @@ static_assert(has_shape<F3x1, false, 4, 1, 6, 1, false>() && hi::SweepOf<F3x1, f
 static_assert(has_shape<D2x1, false, 2, 2, 4, 2, false>() && hi::SweepOf<D2x1, false>::OW == 120);
 
 // ------------------------------------------------------------------ the driver
-template <typename F, bool SPLIT> struct Case {
+// `Strategy`: where the launches' time-dependent values come from (tdv/SinglePassStrategies.hpp)
+template <typename F, bool SPLIT, typename Strategy = stencil::tdv::single_pass::PrecomputeOnHostStrategy> struct Case {
     using Cell = typename F::Cell;
-    using Update = stencil::hip::StencilUpdate<F, SPLIT>;
+    using Update = stencil::hip::StencilUpdate<F, SPLIT, Strategy>;
     using Reference = stencil::cpu::StencilUpdate<F>;
     static constexpr bool planes = Update::sweeps_on_planes;
     using Tuning = SweepTuning<F, planes>;
     static constexpr int K = Tuning::cells_per_lane, T = Tuning::max_generations;
     static constexpr int G = int(F::stencil_radius) * int(F::n_subiterations) * T;
     static constexpr int OW = hi::SweepOf<F, planes>::OW;
+    static constexpr int GX = (hi::wave_size * K - OW) / 2; // the column halo, rounded to whole lanes
     static constexpr bool narrow = hi::has_narrow_form<F, planes>();
     static constexpr int OWn = [] {
         if constexpr (narrow)
@@ -329,7 +347,8 @@ template <typename F, bool SPLIT> struct Case {
         }
     }
 
-    void run() {
+    // `more_generations`: run lengths of a case's own besides the ones every case sweeps
+    void run(std::vector<std::size_t> more_generations = {}) {
         // the smallest grids at which a strip seam, a ragged last lane, a one-row grid and a launch of several row
         // chunks can each go wrong, all derived from the shape
         std::vector<std::size_t> widths = {1, 2, K + 1, OW - 1, OW, OW + 1, 2 * OW + 3};
@@ -338,12 +357,37 @@ template <typename F, bool SPLIT> struct Case {
         widths = unique_sorted(widths);
         const std::size_t heights[4] = {1, 3, G + 1, 4 * G + 7};
         // every compiled depth and the mixes (T = 1: no generation at all is a case as well)
-        const std::vector<std::size_t> generations = unique_sorted({1, 2, 3, T - 1, T, T + 1, 2 * T + 3});
+        more_generations.insert(more_generations.end(), {1, 2, 3, T - 1, T, T + 1, 2 * T + 3});
+        const std::vector<std::size_t> generations = unique_sorted(more_generations);
         for (std::size_t i = 0; i < widths.size(); i++)
             for (std::size_t h : {heights[i % 4], heights[(i + 2) % 4]}) { // every width and every height occurs
                 Pair grids = make_grids(h, widths[i]);
                 for (std::size_t n : generations)
                     advance(grids, n, 0, false, "");
+            }
+        // Grids on which units of the wave grid run the check-free code (Sweep::entry(): a unit whose whole footprint
+        // lies inside the grid).  The widest grid above, 2 OW + 3, is narrower than the first one where strip 1 has its
+        // footprint inside, 2 OW + GX: its columns are [OW - GX, 2 OW + GX) and GX is 4 at the least.  So, per form: the
+        // width at which strip 1 just misses, the one at which it just fits, and two check-free strips with a ragged
+        // third; with the chunks of eight rows of the chunks-of-8-rows environment and a = ceil(G / 8) * 8, the chunk
+        // [a, a + 8) is the first whose warm-up rows lie inside the grid, and it needs a + 8 + G rows: one row less
+        // (no chunk qualifies), exactly that (one does), and 4 G + 7.  Every width meets the height at which one chunk
+        // qualifies; the width that just fits meets the height that just misses, the two others 4 G + 7.
+        auto check_free_widths = [](int ow, int gx) {
+            return std::vector<std::size_t>{std::size_t(2 * ow + gx - 1), std::size_t(2 * ow + gx), std::size_t(3 * ow + gx + 1)};
+        };
+        std::vector<std::size_t> wide = check_free_widths(OW, GX);
+        if constexpr (narrow) {
+            const std::vector<std::size_t> more = check_free_widths(OWn, (hi::wave_size * hi::ceil_pow2(int(F::stencil_radius)) - OWn) / 2);
+            wide.insert(wide.end(), more.begin(), more.end());
+        }
+        const std::size_t a = std::size_t((G + 7) / 8 * 8);
+        const std::size_t tall[3] = {a + 8 + G - 1, a + 8 + G, 4 * std::size_t(G) + 7};
+        for (std::size_t i = 0; i < wide.size(); i++)
+            for (std::size_t h : {tall[1], i % 3 == 1 ? tall[0] : tall[2]}) {
+                Pair grids = make_grids(h, wide[i]);
+                for (std::size_t n : generations)
+                    advance(grids, n, 0, false, " (check-free)");
             }
         {
             Pair grids = make_grids(G + 1, OW + 1);
@@ -356,15 +400,16 @@ template <typename F, bool SPLIT> struct Case {
             advance(grids, 3, T + 1, true, " (resumed)");
         }
         std::printf("shape %s: K=%d T=%d P=%d stages=%d narrow=%d planes=%d OW=%d depth=%u\n", name, K, T,
-                    Tuning::prefetch_rows, Tuning::stages, int(narrow), int(planes), OW,
+                    Tuning::prefetch_rows, hi::stages_for<F, planes>(), int(narrow), int(planes), OW,
                     unsigned(Update::sweep_description().max_generations));
         std::fflush(stdout);
     }
 };
 
-template <typename F, bool SPLIT = false> void run_case(const char *name, u32 seed) {
-    Case<F, SPLIT> c(name, seed);
-    c.run();
+template <typename F, bool SPLIT = false, typename Strategy = stencil::tdv::single_pass::PrecomputeOnHostStrategy>
+void run_case(const char *name, u32 seed, std::vector<std::size_t> more_generations = {}) {
+    Case<F, SPLIT, Strategy> c(name, seed);
+    c.run(more_generations);
 }
 
 } // namespace shapes

@@ -1,7 +1,7 @@
 // The reference of the shape coverage, pinned on the host: stencil::cpu::StencilUpdate on every functor of
-// shape_cases.hpp against a plain double loop over two arrays that substitutes the halo, steps through the sub-iterations
+// shape_cases.hpp and hook_cases.hpp (the one-way read policy and the copied constant field among them) against a plain double loop over two arrays that substitutes the halo, steps through the sub-iterations
 // and the generations and evaluates the time-dependent value by hand (no Stencil object).  g++, runs anywhere.
-#include "shape_cases.hpp"
+#include "hook_cases.hpp"
 
 using namespace shapes;
 
@@ -58,6 +58,15 @@ template <typename F> static void pin_reference(const char *name, u32 seed, std:
             changed = changed || !(field<0>(before) == field<0>(after));
         }
     REQUIRE(changed || n == 0);
+    // ... except in the fields the functor declares constant: the last field of such a cell never changes
+    if constexpr (requires { F::constant_fields; }) {
+        constexpr int last = n_fields<Cell>() - 1;
+        bool kept = true;
+        for (std::size_t r = 0; r < h; r++)
+            for (std::size_t c = 0; c < w; c++)
+                kept = kept && field<last>(initial_cell<Cell>(u32(r), u32(c), seed)) == field<last>(now[r * w + c]);
+        REQUIRE(kept);
+    }
 }
 
 template <typename F> static void pin(const char *name, u32 seed) {
@@ -81,5 +90,22 @@ int main() {
     pin<F2x2>("F2x2", 0x4001u);
     pin<F3x1>("F3x1", 0x4002u);
     pin<D2x1>("D2x1", 0x4003u);
+    pin<Canary>("Canary", 0x5001u);
+    pin<Rim>("Rim", 0x5002u);
+    pin<Levels>("Levels", 0x5003u);
+    pin<OneWayRim>("OneWayRim", 0x5004u);
+    pin<OneWay>("OneWay", 0x5101u);
+    pin<OneWayPlanes>("OneWayPlanes", 0x5102u);
+    pin<Liar>("Liar", 0x5103u);
+    pin<Lone8>("Lone8", 0x5201u);
+    pin<Twelve>("Twelve", 0x5202u);
+    pin<Batch8>("Batch8", 0x5203u);
+    pin<FatOn>("FatOn", 0x5204u);
+    pin<Stateless>("Stateless", 0x5005u);
+    pin<State7>("State7", 0x5302u);
+    pin<State16>("State16", 0x5303u);
+    pin<State36>("State36", 0x5304u);
+    pin<State40>("State40", 0x5305u);
+    pin<StateTable>("StateTable", 0x5306u);
     return finish("shape_host_test");
 }

@@ -15,6 +15,10 @@ STSTHIP_EXCHANGE_EVERY=1 grids one row or column thinner than two ghost depths m
 3 ranks swept as two sub-strips with a moving boundary, at the smallest height the driver accepts for them, for more
 generations than the boundary's span; the launch counters show that every pass ran as two launches.
 
+shape_test_f holds the two functors that declare halo_columns_per_generation (tests/cpp_shapes/hook_cases.hpp: one-way
+reads as AoS and on planes with a constant field); its mesh mode runs at STSTHIP_EXCHANGE_EVERY=1, where the drivers'
+ghost depth is radius x sub-iterations per generation while the kernel's column halo is the hint's.
+
 Options are read once per process, so each environment is one case per binary.  A mismatch prints the functor, the
 mesh, every rank's rows and columns, the interval, the generations and the first differing (row, column, field)."""
 import os
@@ -31,7 +35,13 @@ ENVIRONMENTS = {
     "exchange-by-the-rule": WIDE,
     "exchange-every-2": dict(WIDE, STSTHIP_EXCHANGE_EVERY="2"),
 }
-INTERVAL = {"exchange-every-launch": "1", "exchange-by-the-rule": "rule", "exchange-every-2": "2"}
+# the functors with a column hint: every launch exchanges; at every compiled depth, because the spill-free depth of the
+# one on planes is 1 (tests/test_template_hooks_gpu.py, SPILLING), where the hint changes nothing
+HINTED = {"shape_test_f": ["OneWay", "OneWayPlanes/planes"]}
+ENVIRONMENTS["exchange-every-launch-hinted"] = dict(ENVIRONMENTS["exchange-every-launch"], STSTHIP_ALLOW_SPILLING_DEPTHS="1")
+MESH_CASES = [pytest.param(b, e, id=f"{b}-{e}") for b in BINARIES for e in ENVIRONMENTS if not e.endswith("-hinted")]
+MESH_CASES += [pytest.param(b, "exchange-every-launch-hinted", id=f"{b}-exchange-every-launch") for b in HINTED]
+INTERVAL = {"exchange-every-launch": "1", "exchange-every-launch-hinted": "1", "exchange-by-the-rule": "rule", "exchange-every-2": "2"}
 SUBSTRIPS = dict(WIDE, STSTHIP_EXCHANGE_EVERY="2", STSTHIP_STRIP_SUBSTRIPS="2", STSTHIP_SKEWED_STRIPS="1")
 MESH_KNOBS = KNOBS + ("STSTHIP_EXCHANGE_EVERY", "STSTHIP_STRIP_SUBSTRIPS", "STSTHIP_SKEWED_STRIPS", "STSTHIP_VIRTUAL_STRIPS")
 
@@ -60,11 +70,10 @@ def report_of(text, mode, functor):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,environment",
-                         [pytest.param(b, e, id=f"{b}-{e}") for b in BINARIES for e in ENVIRONMENTS])
+@pytest.mark.parametrize("name,environment", MESH_CASES)
 def test_every_shape_on_strips_and_meshes_equals_the_cpu_backend(name, environment):
     text = run_mode(name, "mesh", ENVIRONMENTS[environment])
-    for functor in BINARIES[name]:
+    for functor in dict(BINARIES, **HINTED)[name]:
         report = report_of(text, "mesh", functor)
         D, hpg, g = (int(report.group(i)) for i in (1, 2, 3))
         assert g == D * hpg and report.group(4) == INTERVAL[environment]
@@ -72,7 +81,7 @@ def test_every_shape_on_strips_and_meshes_equals_the_cpu_backend(name, environme
         for decomposition in ("strips1", "strips2", "strips3", "mesh1x1", "mesh1x2", "mesh2x1", "mesh2x2", "mesh1x3",
                               "mesh3x1", "mesh3x3"):
             assert f" {decomposition}:" in extents, f"{functor}: {decomposition} did not run\n{report.group(0)}"
-        if environment == "exchange-every-launch":
+        if environment.startswith("exchange-every-launch"):
             # at the limit: every rank owns exactly two ghost depths along every cut axis
             assert f" strips2:{4 * g}x" in extents and f" strips3:{6 * g}x" in extents, report.group(0)
             assert f" mesh2x2:{4 * g}x{4 * g}" in extents and f" mesh3x3:{6 * g}x{6 * g}" in extents, report.group(0)

@@ -4,7 +4,12 @@ stencil::hip::StencilUpdate and compared with stencil::cpu::StencilUpdate field 
 
 Each binary holds three cases and sweeps, per case, ten widths around the strip seams of the default and the narrow
 form, each at two of four heights (one row ... several row chunks), for 1, 2, 3, T-1, T, T+1 and 2T+3 generations,
-then a run from iteration 5 and a second call resumed through get_params().  Every functor is a position-sensitive
+then a run from iteration 5 and a second call resumed through get_params(); and the grids on which units of the wave
+grid run the check-free code (their whole footprint inside the grid), which the widths above never reach: 2 OW + GX - 1
+columns (strip 1 just misses), 2 OW + GX (just fits) and 3 OW + GX + 1 (two such strips and a ragged third), for the
+narrow form as well, at a + 8 + G - 1 rows (a = G rounded up to 8: with chunks of eight rows no chunk qualifies),
+a + 8 + G (one does) and 4 G + 7.  tests/test_template_hooks_gpu.py proves with a canary which units of those grids
+run that code.  Every functor is a position-sensitive
 hash of its neighbourhood, so a neighbour from the wrong lane, row, level or generation changes cells; a mismatch
 prints the functor, the grid, the generations, the depth and the first differing (row, column, field).
 
