@@ -66,6 +66,65 @@ template <bool FirstLaunch, bool LastLaunch> struct Jacobi5Uniform : public Base
             return c * sum;
     }
 
+#if defined(__clang__)
+    // The same level for a lane's whole row of four cells at once (the sweep's row-form hook, Sweep.hpp: check-free
+    // waves with four cells per lane).  The rows arrive in LANE ORDER (c0, c2, c1, c3): the register pairs A = (c0, c2)
+    // and B = (c1, c3) are then each other's west and east neighbours, so twelve of a row's sixteen additions and
+    // its four multiplications are packed instructions (v_pk_add_f32 / v_pk_mul_f32: two operations per issue slot).
+    // Per cell these are at_level's operations on at_level's values in at_level's order, ((((n + w) + s) + e) + x) and c * sum,
+    // every one rounded on its own: bit for bit the same results (tests/test_packed_rows_cpu.py).
+    // `sh.west(v)` / `sh.east(v)`: v as held by the lane to the west / east.
+    typedef float Pair __attribute__((ext_vector_type(2)));
+    // The four additions that take ONE neighbour-lane operand stay plain: left alone the compiler packs them as well
+    // and builds their operand pairs with moves (57 v_mov per batch of the headline kernel instead of 8); a value
+    // that has passed through an empty asm statement is opaque to that, and the lane shift still folds onto the add.
+    STST_HD static float plain(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(v));
+#endif
+        return v;
+    }
+    template <int level, int levels, typename Shifts>
+    STST_HD void row_at_level(Shifts sh, float const (&north)[4], float const (&centre)[4], float const (&south)[4],
+                              float (&out)[4]) const {
+#pragma clang fp contract(off)
+        constexpr bool raw_inputs = FirstLaunch && level == 0;
+        constexpr bool raw_output = LastLaunch && level == levels - 1;
+        Pair nA = {north[0], north[1]}, nB = {north[2], north[3]};
+        Pair mA = {centre[0], centre[1]}, mB = {centre[2], centre[3]};
+        Pair sA = {south[0], south[1]}, sB = {south[2], south[3]};
+        float wl = sh.west(centre[3]); // c3 of the lane to the west
+        float er = sh.east(centre[0]); // c0 of the lane to the east
+        if constexpr (raw_inputs) {
+            nA = c * nA;
+            nB = c * nB;
+            mA = c * mA;
+            mB = c * mB;
+            sA = c * sA;
+            sB = c * sB;
+            wl = c * wl;
+            er = c * er;
+        }
+        Pair tA;
+        tA.x = plain(nA.x + wl);   // c0: n + w, west is the neighbour lane's c3
+        tA.y = plain(nA.y + mB.x); // c2: n + w, west is c1
+        tA = ((tA + sA) + mB) + mA; // east of (c0, c2) is (c1, c3)
+        Pair tB = (nB + mA) + sB;   // west of (c1, c3) is (c0, c2)
+        Pair uB;
+        uB.x = plain(tB.x + mA.y); // c1: + e, east is c2
+        uB.y = plain(tB.y + er);   // c3: + e, east is the neighbour lane's c0
+        uB = uB + mB;
+        if constexpr (!raw_output) {
+            tA = c * tA;
+            uB = c * uB;
+        }
+        out[0] = tA.x;
+        out[1] = tA.y;
+        out[2] = uB.x;
+        out[3] = uB.y;
+    }
+#endif
+
     // one generation on its own is the original expression (first and last level at once)
     STST_HD float operator()(Stencil<float, 1> const &s) const {
 #if defined(__clang__)

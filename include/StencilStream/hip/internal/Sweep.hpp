@@ -210,6 +210,12 @@ template <int DppCtrl, typename T> STST_DEVICE inline T lane_shift(T const &valu
 template <typename T> STST_DEVICE inline T from_west_lane(T const &v) { return lane_shift<0x138>(v); }
 // value of lane+1: DPP wave_shl:1
 template <typename T> STST_DEVICE inline T from_east_lane(T const &v) { return lane_shift<0x130>(v); }
+// the two shifts as an object, handed to a transition function's row form (Sweep::run), which then needs nothing from
+// this namespace
+struct LaneShifts {
+    template <typename T> STST_DEVICE T west(T const &v) const { return from_west_lane(v); }
+    template <typename T> STST_DEVICE T east(T const &v) const { return from_east_lane(v); }
+};
 
 // ------------------------------------------------------------------ tuning
 constexpr int ceil_pow2(int v) {
@@ -443,6 +449,29 @@ template <typename F, bool SOA> constexpr bool scalar_function_for() {
         return SweepTuning<F, SOA>::scalar_function;
     else
         return sizeof(F) % 4 == 0 && sizeof(F) <= 36 && !std::is_empty_v<F>;
+}
+
+// Row form.  A transition function of radius 1 may offer one level for a lane's whole row of four cells,
+//     template <int level, int levels, typename Shifts>
+//     void row_at_level(Shifts sh, Cell const (&north)[4], Cell const (&centre)[4], Cell const (&south)[4],
+//                       Cell (&out)[4]) const;
+// with sh.west(v) / sh.east(v) = v as the lane to the west / east holds it (LaneShifts).  Check-free waves with four
+// cells per lane call it instead of the per-cell at_level / operator(), and keep a lane's cells in LANE ORDER
+// (c0, c2, c1, c3) everywhere between stage 0's load from HBM and the last stage's store: the register pairs
+// (c0, c2) and (c1, c3) are then each other's west and east neighbours, operands of packed fp32 instructions as they
+// lie (forms/Jacobi5Uniform.hpp).  SweepTuning<F, SOA>::row_form = false (optional member) keeps the per-cell path:
+// the A/B of tools/experiments/app_experiments25.hip, profiles/r05_packed_rows.txt.
+template <typename F> constexpr bool has_row_form() {
+    using Cell = typename F::Cell;
+    return requires(F const &f, Cell const(&row)[4], Cell(&out)[4]) {
+        f.template row_at_level<0, 1>(LaneShifts{}, row, row, row, out);
+    };
+}
+template <typename F, bool SOA> constexpr bool row_form_for() {
+    if constexpr (requires { SweepTuning<F, SOA>::row_form; })
+        return SweepTuning<F, SOA>::row_form && has_row_form<F>();
+    else
+        return has_row_form<F>();
 }
 
 template <typename F, bool SOA> constexpr bool trapezoid_fill_for() {
@@ -698,6 +727,11 @@ struct Sweep {
                                 LdsWord *lds) {
         constexpr std::uint32_t skip_mask = SKIP_CONSTANTS ? constant_plane_mask<F>() : 0u;
         constexpr int L0 = SG * L; // levels below this stage
+        // Row form (has_row_form above): this wave keeps a lane's four cells in lane order (c0, c2, c1, c3) in pre[],
+        // cur, win[][][] and the LDS rings.  All waves of a unit take the same EDGE branch, so the stages on either side
+        // of a ring agree; the order is applied behind stage 0's load from HBM and undone in front of the last stage's
+        // store, nowhere else (the halo fill below is uniform).
+        constexpr bool ROWS = !EDGE && K == 4 && R == 1 && row_form_for<F, SOA>();
         // (read where the kernel's arguments lie: indexing the tier tables at run time must not cost a private copy)
         SweepGeometry const &g = *(SweepGeometry const *)(const SweepGeometry __attribute__((address_space(4))) *)(
             (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(Args, geo));
@@ -770,6 +804,11 @@ struct Sweep {
                 row_offset(g, yc) + std::size_t(std::int64_t(x0 - g.col_origin));
             if constexpr (!EDGE) {
                 a.src.template load<K>(first, into);
+                if constexpr (ROWS) { // into lane order
+                    const Cell c1 = into[1];
+                    into[1] = into[2];
+                    into[2] = c1;
+                }
             } else {
                 if (vec_in) {
                     a.src.template load<K>(first, into);
@@ -830,6 +869,18 @@ struct Sweep {
                             live = false;
                             return;
                         }
+                    }
+                    if constexpr (ROWS) {
+                        // the whole row at once: north and centre are the window's two rows, south is `cur`
+                        Cell next[K];
+                        fn.template row_at_level<level - 1, S>(LaneShifts{}, win[lc][oldest],
+                                                               win[lc][(oldest + 1) % NWIN], cur, next);
+#pragma unroll
+                        for (int k = 0; k < K; k++) {
+                            win[lc][oldest][k] = cur[k];
+                            cur[k] = next[k];
+                        }
+                        return;
                     }
                     const int j = y - level * R;            // global row this level emits now
                     const std::size_t iteration = g.iteration + std::size_t((level - 1) / NS);
@@ -940,7 +991,12 @@ struct Sweep {
                         if (!EDGE || vec_out) {
                             if constexpr (W > 1 && pinned_stores_for<F, SOA>())
                                 __builtin_amdgcn_sched_barrier(0);
-                            a.dst.template store<K, streaming_stores_for<F, SOA>(), skip_mask>(first, cur);
+                            if constexpr (ROWS) { // back from lane order
+                                const Cell row[4] = {cur[0], cur[2], cur[1], cur[3]};
+                                a.dst.template store<4, streaming_stores_for<F, SOA>(), skip_mask>(first, row);
+                            } else {
+                                a.dst.template store<K, streaming_stores_for<F, SOA>(), skip_mask>(first, cur);
+                            }
                             if constexpr (W > 1 && pinned_stores_for<F, SOA>())
                                 __builtin_amdgcn_sched_barrier(0);
                         } else {
