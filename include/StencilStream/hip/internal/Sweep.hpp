@@ -461,6 +461,13 @@ template <typename F, bool SOA> constexpr bool scalar_function_for() {
 // (c0, c2) and (c1, c3) are then each other's west and east neighbours, operands of packed fp32 instructions as they
 // lie (forms/Jacobi5Uniform.hpp).  SweepTuning<F, SOA>::row_form = false (optional member) keeps the per-cell path:
 // the A/B of tools/experiments/app_experiments25.hip, profiles/r05_packed_rows.txt.
+// Edge waves -- units whose footprint leaves the grid -- take the row form as well: the cells outside the grid are set
+// back to the halo value behind every level, one select per cell (the row test is wave-uniform and folds into the
+// lanes' column masks with scalar instructions).  Units whose columns all lie inside (Sweep::entry: cols_inside, the
+// units at the grid's first and last rows) have no column masks and run the batches that lie inside the grid with all
+// their rows in a loop that tests nothing.  Wherever the edge code names a lane's cell by its column it goes through
+// `lane_order`.  SweepTuning<F, SOA>::row_form_edges = false (optional member) keeps the per-cell path in edge waves:
+// the A/B of tools/experiments/app_experiments26.hip, profiles/r06_edge_rows.txt.
 template <typename F> constexpr bool has_row_form() {
     using Cell = typename F::Cell;
     return requires(F const &f, Cell const(&row)[4], Cell(&out)[4]) {
@@ -473,6 +480,15 @@ template <typename F, bool SOA> constexpr bool row_form_for() {
     else
         return has_row_form<F>();
 }
+
+template <typename F, bool SOA> constexpr bool row_form_edges_for() {
+    if constexpr (requires { SweepTuning<F, SOA>::row_form_edges; })
+        return SweepTuning<F, SOA>::row_form_edges && row_form_for<F, SOA>();
+    else
+        return row_form_for<F, SOA>();
+}
+// position of column k of a lane's four cells in lane order (c0, c2, c1, c3); its own inverse
+constexpr int lane_order[4] = {0, 2, 1, 3};
 
 template <typename F, bool SOA> constexpr bool trapezoid_fill_for() {
     if constexpr (requires { SweepTuning<F, SOA>::trapezoid_fill; })
@@ -656,6 +672,13 @@ struct Sweep {
     static constexpr int IFACE_WORDS = 2 * P * ROW_WORDS;   // two batches of P rows
     static constexpr int LDS_WORDS = W > 1 ? (W - 1) * IFACE_WORDS : 1;
     static constexpr int lane_align = (LANE_WORDS % 4 == 0) ? 16 : ((LANE_WORDS % 2 == 0) ? 8 : 4);
+    // which waves call a function's row form (has_row_form): check-free ones, and edge ones unless the tuning says no
+    static constexpr bool ROW_FORM = K == 4 && R == 1 && row_form_for<F, SOA>();
+    static constexpr bool EDGE_ROW_FORM = K == 4 && R == 1 && row_form_edges_for<F, SOA>();
+    // ... and whether the edge units whose columns all lie inside the grid get code of their own (run: COLS_INSIDE): at
+    // the function's deepest depth, where nearly all generations of a run are swept.  The shallower depths run a call's
+    // last launches; there the third copy of the stages' code cost 2-4 VGPRs (T = 8: 60 -> 62, T = 1: 55 -> 57).
+    static constexpr bool COLS_INSIDE_VARIANT = EDGE_ROW_FORM && T == SweepTuning<F, SOA>::max_generations;
 
     static_assert(K >= R, "a lane must hold at least `radius` cells so neighbours are one lane away");
     static_assert(OW >= K, "halo consumes the whole strip: lower max_generations or raise K");
@@ -722,7 +745,9 @@ struct Sweep {
     // constant_plane_mask); their stores are left out
     // (always inlined: as a called function a stage would receive the kernel's arguments through a private copy in
     // scratch memory -- seen for large transition functions at depths of 4 and more)
-    template <bool EDGE, bool SKIP_CONSTANTS, int SG>
+    // COLS_INSIDE (edge waves of the row form only): every column of the unit's footprint lies inside the grid and the
+    // buffers and is a column to produce or halo of one -- a unit at the grid's first or last rows; only rows are tested
+    template <bool EDGE, bool SKIP_CONSTANTS, int SG, bool COLS_INSIDE = false>
     STST_DEVICE __attribute__((always_inline)) static void run(Args const &a, const int lane, const int strip, const int ya, const int yb,
                                 LdsWord *lds) {
         constexpr std::uint32_t skip_mask = SKIP_CONSTANTS ? constant_plane_mask<F>() : 0u;
@@ -730,8 +755,9 @@ struct Sweep {
         // Row form (has_row_form above): this wave keeps a lane's four cells in lane order (c0, c2, c1, c3) in pre[],
         // cur, win[][][] and the LDS rings.  All waves of a unit take the same EDGE branch, so the stages on either side
         // of a ring agree; the order is applied behind stage 0's load from HBM and undone in front of the last stage's
-        // store, nowhere else (the halo fill below is uniform).
-        constexpr bool ROWS = !EDGE && K == 4 && R == 1 && row_form_for<F, SOA>();
+        // store, and wherever the edge code names a cell by its column: lane_order[k] (the halo fill below is uniform).
+        constexpr bool ROWS = EDGE ? EDGE_ROW_FORM : ROW_FORM;
+        static_assert(!COLS_INSIDE || (EDGE && ROWS));
         // (read where the kernel's arguments lie: indexing the tier tables at run time must not cost a private copy)
         SweepGeometry const &g = *(SweepGeometry const *)(const SweepGeometry __attribute__((address_space(4))) *)(
             (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + __builtin_offsetof(Args, geo));
@@ -742,12 +768,13 @@ struct Sweep {
         bool col_in[K];
 #pragma unroll
         for (int k = 0; k < K; k++)
-            col_in[k] = unsigned(x0 + k - g.col_lo) < unsigned(g.col_hi - g.col_lo);
+            col_in[k] = COLS_INSIDE || unsigned(x0 + k - g.col_lo) < unsigned(g.col_hi - g.col_lo);
         // (columns of the grid the buffers do not hold -- beyond the ghost columns of a block -- are treated like
         // columns outside the grid: never loaded; they cannot reach a column this launch stores)
-        const bool vec_in = x0 >= g.col_lo && x0 + K <= g.col_hi;
+        const bool vec_in = COLS_INSIDE || (x0 >= g.col_lo && x0 + K <= g.col_hi);
         const bool lane_stores = lane * K >= GX && lane * K + K <= LW - GX;
-        const bool vec_out = vec_in && x0 + K <= g.out_col_end; // the last strip of a column range may be ragged
+        // the last strip of a column range may be ragged (COLS_INSIDE: not in a lane that stores)
+        const bool vec_out = COLS_INSIDE || (vec_in && x0 + K <= g.out_col_end);
 
         // The launch's time-dependent values: the call's device table, or the kernel arguments (Args::tdv sits at
         // offset 0 of the kernel's argument segment).  Both are read through the constant address space -- nothing
@@ -802,7 +829,7 @@ struct Sweep {
             yc = yc < y_load_end ? yc : y_load_end - 1;
             const std::size_t first =
                 row_offset(g, yc) + std::size_t(std::int64_t(x0 - g.col_origin));
-            if constexpr (!EDGE) {
+            if constexpr (!EDGE || COLS_INSIDE) {
                 a.src.template load<K>(first, into);
                 if constexpr (ROWS) { // into lane order
                     const Cell c1 = into[1];
@@ -812,11 +839,16 @@ struct Sweep {
             } else {
                 if (vec_in) {
                     a.src.template load<K>(first, into);
+                    if constexpr (ROWS) {
+                        const Cell c1 = into[1];
+                        into[1] = into[2];
+                        into[2] = c1;
+                    }
                 } else {
 #pragma unroll
                     for (int k = 0; k < K; k++)
                         if (col_in[k])
-                            a.src.load_one(first + k, into[k]);
+                            a.src.load_one(first + k, into[ROWS ? lane_order[k] : k]);
                 }
             }
         };
@@ -831,7 +863,11 @@ struct Sweep {
         // stage receives at `step` is what level L0 emitted for it.  While the pipeline fills (FILLING) level l only
         // has to produce rows from step 2*l*R on -- earlier outputs cannot reach a stored row -- so the deeper levels
         // are skipped by wave-uniform branches: a trapezoid of level-steps instead of a parallelogram.
-        auto row_step = [&](auto u, const int it, auto filling, const int ring) __attribute__((always_inline)) {
+        // ROWS_INSIDE (COLS_INSIDE only): every row this stage takes in or emits in this batch lies inside the grid -- all
+        // but the first or last batches of a unit at the grid's first or last rows --, so nothing is tested.  (A template
+        // argument that is only looked at inside `if constexpr (EDGE)`: a parameter, or a condition that depends on the
+        // argument around the edge code, changes what the closure captures and with it the code of every other kernel.)
+        auto row_step = [&]<bool ROWS_INSIDE = false>(auto u, const int it, auto filling, const int ring) __attribute__((always_inline)) {
                 constexpr bool FILLING = decltype(filling)::value;
                 const int step = it + u;
                 const int y = ystart + step; // global row entering level 1 at this step
@@ -846,11 +882,13 @@ struct Sweep {
                     if constexpr (W > 1 && pinned_loads_for<F, SOA>())
                         __builtin_amdgcn_sched_barrier(0);
                     if constexpr (EDGE) {
-                        const bool row_in = unsigned(y) < unsigned(g.grid_h);
+                        if constexpr (!ROWS_INSIDE) {
+                            const bool row_in = unsigned(y) < unsigned(g.grid_h);
 #pragma unroll
-                        for (int k = 0; k < K; k++)
-                            if (!(row_in && col_in[k]))
-                                cur[k] = a.halo;
+                            for (int k = 0; k < K; k++)
+                                if (!(row_in && col_in[k]))
+                                    cur[ROWS ? lane_order[k] : k] = a.halo;
+                        }
                     }
                 }
 
@@ -875,6 +913,21 @@ struct Sweep {
                         Cell next[K];
                         fn.template row_at_level<level - 1, S>(LaneShifts{}, win[lc][oldest],
                                                                win[lc][(oldest + 1) % NWIN], cur, next);
+                        if constexpr (EDGE && !ROWS_INSIDE) {
+                            // out-of-grid cells never evolve; the row test is wave-uniform and folds into the lanes'
+                            // column masks with scalar instructions: one select per cell
+                            const int j = y - level * R; // global row this level emits now
+                            const bool row_in = unsigned(j) < unsigned(g.grid_h);
+#pragma unroll
+                            for (int k = 0; k < K; k++) {
+                                // (a result that came out of a packed instruction: selected as the scalar it is here, or
+                                // the compiler selects on the pair and leaves three selects per row that select nothing)
+                                if constexpr (sizeof(Cell) == 4 && std::is_arithmetic_v<Cell>)
+                                    asm volatile("" : "+v"(next[lane_order[k]]));
+                                if (!(row_in && col_in[k]))
+                                    next[lane_order[k]] = a.halo;
+                            }
+                        }
 #pragma unroll
                         for (int k = 0; k < K; k++) {
                             win[lc][oldest][k] = cur[k];
@@ -1003,7 +1056,7 @@ struct Sweep {
 #pragma unroll
                             for (int k = 0; k < K; k++)
                                 if (col_in[k] && x0 + k < g.out_col_end)
-                                    a.dst.template store_one<skip_mask>(first + k, cur[k]);
+                                    a.dst.template store_one<skip_mask>(first + k, cur[ROWS ? lane_order[k] : k]);
                         }
                     }
                 } else {
@@ -1026,7 +1079,8 @@ struct Sweep {
         const int n_rows_in = yb - ya + 2 * G;
         const int n_batches = (n_rows_in + P - 1) / P;
         const int n_super = n_batches + (W - 1);
-        auto super_step = [&](const int t, auto filling) __attribute__((always_inline)) {
+        // BATCH: whether the caller knows that the stage has a batch in this super-step (1), has none (-1), or not (0)
+        auto super_step = [&]<bool ROWS_INSIDE = false, int BATCH = 0>(const int t, auto filling) __attribute__((always_inline)) {
             if constexpr (W > 1) {
                 // rows of the previous super-step become visible to the next stage; LDS only -- the rows in flight
                 // from HBM (pre[]) must not be waited for here
@@ -1040,14 +1094,22 @@ struct Sweep {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
             }
             const int b = t - SG;
-            if (b < first_batch || b >= n_batches)
+            if constexpr (BATCH < 0)
                 return;
+            if constexpr (BATCH == 0)
+                if (b < first_batch || b >= n_batches)
+                    return;
             const int ring = (b & 1) * P;
             if constexpr (SG > 0)
                 static_for<0, P>([&](auto u) __attribute__((always_inline)) {
                     lds_load_row(lds, SG - 1, ring + u, lane, pre[u]);
                 });
-            static_for<0, P>([&](auto u) __attribute__((always_inline)) { row_step(u, b * P, filling, ring); });
+            if constexpr (ROWS_INSIDE)
+                static_for<0, P>([&](auto u) __attribute__((always_inline)) {
+                    row_step.template operator()<true>(u, b * P, filling, ring);
+                });
+            else
+                static_for<0, P>([&](auto u) __attribute__((always_inline)) { row_step(u, b * P, filling, ring); });
         };
         int t = 0;
         if constexpr (TRAPEZOID) {
@@ -1057,8 +1119,41 @@ struct Sweep {
             for (; t < t_fill; t++)
                 super_step(t, std::true_type{});
         }
-        for (; t < n_super; t++)
-            super_step(t, std::false_type{});
+        if constexpr (COLS_INSIDE) {
+            // Batches [b_lo, b_hi) lie inside the grid with all their rows: the batch's P input rows, first row
+            // y = ystart + b * P, at the levels L0 (what this stage takes in) to L0 + L (its last level emits row
+            // y - (L0 + L) * R).  The batches before and behind them -- a unit at the grid's first rows has some before,
+            // one at its last rows some behind -- run the tested code; loops of their own, so that the check-free
+            // batches in between keep the registers of the check-free code.
+            const int above = (L0 + L) * R - ystart;          // y - (L0 + L) * R >= 0
+            const int below = g.grid_h + L0 * R - ystart - P; // y + P - 1 - L0 * R < grid_h
+            const int b_lo = above > 0 ? (above + P - 1) / P : 0;
+            int b_hi = below >= 0 ? below / P + 1 : 0;
+            b_hi = b_hi < n_batches ? b_hi : n_batches;
+            const int t_lo = b_lo + SG < n_super ? b_lo + SG : n_super;
+            const int t_hi = b_hi + SG > t_lo ? b_hi + SG : t_lo;
+            for (int part = 0; part < 2; part++) {
+                const int t_tested = part == 0 ? t_lo : n_super;
+                for (; t < t_tested; t++)
+                    super_step(t, std::false_type{});
+                if (part == 0)
+                    for (; t < t_hi; t++)
+                        super_step.template operator()<true, 1>(t, std::false_type{});
+            }
+        } else if constexpr (EDGE && ROWS && W > 1) {
+            // the super-steps without a batch of this stage -- SG before its first one, W - 1 - SG behind its last --
+            // in loops of their own: with the test inside, the one loop copied the stage's window from register to
+            // register once per batch (32 moves in one of the two middle stages)
+            for (; t < SG && t < n_super; t++)
+                super_step.template operator()<false, -1>(t, std::false_type{});
+            for (; t < SG + n_batches; t++)
+                super_step.template operator()<false, 1>(t, std::false_type{});
+            for (; t < n_super; t++)
+                super_step.template operator()<false, -1>(t, std::false_type{});
+        } else {
+            for (; t < n_super; t++)
+                super_step(t, std::false_type{});
+        }
     }
 
     // The kernel's argument block where it lies (the kernel-argument segment, constant address space).  The device code
@@ -1113,12 +1208,22 @@ struct Sweep {
         const bool interior = INTERIOR_VARIANT && xw0 > 0 && xw0 >= g.col_lo && xw0 + LW <= g.col_hi &&
                               xw0 + LW - GX <= g.out_col_end && ya - G >= 0 && yb + G <= g.grid_h &&
                               (!hinted_interior || xw0 + LW < g.grid_w);
+        // (edge waves of the row form) no column test in a unit whose footprint lies inside the columns: vector loads
+        // and stores throughout, no lane holds a column outside the grid
+        const bool cols_inside = COLS_INSIDE_VARIANT && xw0 >= g.col_lo && xw0 + LW <= g.col_hi && xw0 + LW - GX <= g.out_col_end;
         // the stage of a wave is a compile-time property of the code it runs (levels, iteration and sub-iteration
         // indices, fused forms): one instantiation per stage, selected by the wave's index in the workgroup
         static_for<0, W>([&](auto sg) __attribute__((always_inline)) {
             if (W > 1 && wib != int(sg))
                 return;
-            if constexpr (INTERIOR_VARIANT) {
+            if constexpr (COLS_INSIDE_VARIANT) {
+                if (INTERIOR_VARIANT && interior)
+                    run<false, SKIP_CONSTANTS, int(sg)>(a, lane, strip, ya, yb, lds);
+                else if (cols_inside)
+                    run<true, SKIP_CONSTANTS, int(sg), true>(a, lane, strip, ya, yb, lds);
+                else
+                    run<true, SKIP_CONSTANTS, int(sg)>(a, lane, strip, ya, yb, lds);
+            } else if constexpr (INTERIOR_VARIANT) {
                 if (interior)
                     run<false, SKIP_CONSTANTS, int(sg)>(a, lane, strip, ya, yb, lds);
                 else
