@@ -515,6 +515,66 @@ typedef struct {
 int ststhip_grid_dot(int n, const ststhip_grid_dot_desc *pairs, ststhip_grid_dot_result *result,
                      ststhip_stream stream);
 
+/* Grid relaxation: red-black sweeps of the five-point operator IN PLACE (an extension, as the stencils; additive within
+ * ABI 6).  The smoother of a multigrid cycle without a second grid: ststhip_grid_stencil refuses src == dst, because a
+ * stencil in place is a race; a cell of one colour has only neighbours of the other colour, so updating one colour at
+ * a time is race-free by construction and the result is one defined set of bits.  Views and element types are the
+ * algebra's.
+ *
+ * Colour.  The colour of cell (r, q) in VIEW coordinates is (r + q + parity) & 1.  It does not depend on the
+ * rectangle, so tiles of one grid agree; a rank of a strip run passes the parity of its first row's global index.
+ *
+ * Half-sweeps.  Half-sweep k, for k = 0 .. n_half_sweeps - 1, updates exactly the cells of the n_rows x n_cols
+ * rectangle (from (u_row, u_col) on) whose colour is (first_colour + k) & 1; a full Gauss-Seidel sweep is
+ * n_half_sweeps = 2.  The half-sweeps of one entry are ordered among themselves.
+ *
+ * The update is DEFINED OPERATION BY OPERATION and is exactly the stencil's CROSS5.  For such a cell (u_row + i,
+ * u_col + j) with its neighbours N (row - 1), W (column - 1), C (itself), E (column + 1), S (row + 1):
+ *     acc = w_n * N;  acc = acc + w_w * W;  acc = acc + w_c * C;  acc = acc + w_e * E;  acc = acc + w_s * S;
+ *     if has_rhs:     acc = acc + rhs_coef * rhs(rhs_row + i, rhs_col + j);
+ *     u(u_row + i, u_col + j) = acc
+ * with weight = {w_n, w_w, w_c, w_e, w_s}.  Every product and every sum is rounded once in the element's type and
+ * never fused; subnormals are kept.  Weights, rhs_coef and halo are converted from double once, on the host.  EVERY
+ * tap is multiplied, also one whose weight is zero: 0 * inf is NaN, as in numpy.  A neighbour outside the VIEW reads
+ * `halo`; one outside the rectangle but inside the view reads the view and is never written by this entry, so that
+ * tiles and strips compose.  All four neighbours have the other colour: a half-sweep reads only values that the
+ * previous half-sweep left.  Cells of the other colour, and everything outside the rectangle, keep their bytes.
+ * SOR with factor omega for (4 u - N - W - E - S) / h^2 = f is weight = {omega/4, omega/4, 1 - omega, omega/4,
+ * omega/4}, rhs_coef = omega h^2 / 4; omega = 1 is Gauss-Seidel.
+ *
+ * The conventions are the stencil's: one to eight entries per call, run in NO particular order and not checked against
+ * each other (two entries that touch each other's cells are the caller's problem); nothing is clipped; an empty
+ * rectangle succeeds on the host, also with null bases and without a device; n_rows, n_cols and the byte extent of a
+ * rectangle's row in either view are below 2^31; bases and strides are multiples of the element's size; the call is
+ * ordered on `stream` and does not synchronise.
+ *
+ * Overlap.  What the entry reads or writes of u is the rectangle widened by one cell on every side where that lies
+ * inside the view.  rhs may be another member of u's cells by the regions' rule (same stride and pitch, the first
+ * elements of the two rectangles d bytes apart with elem_size <= d and d + elem_size <= stride).  Every other
+ * intersection of rhs's byte span with that of the widened rectangle is refused, rhs being u itself included.
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID, ststhip_last_error() starts with
+ * "grid relax"): n outside 1..8, an unknown type, first_colour or parity above 1, n_half_sweeps outside 1..1024,
+ * reserved != 0, stride 0, pitch < width, a null base with a non-empty rectangle, misalignment, extents that describe
+ * more than 2^63 bytes, a rectangle outside its view, a weight or (with has_rhs) an rhs_coef that is not finite (a halo
+ * may be anything), the limits and the overlap rule above.  With has_rhs == 0, rhs, rhs_row, rhs_col and rhs_coef are
+ * ignored. */
+typedef struct {
+    ststhip_grid_view u, rhs;        /* u is read and written; rhs ignored when has_rhs == 0 */
+    uint32_t type;                   /* STSTHIP_F32 or STSTHIP_F64            */
+    uint32_t has_rhs;
+    uint32_t first_colour;           /* 0 or 1: the colour of half-sweep 0    */
+    uint32_t n_half_sweeps;          /* 1 .. 1024, run in order, colours alternating */
+    uint32_t parity, reserved;       /* parity 0 or 1; reserved = 0           */
+    uint64_t u_row, u_col;           /* the rectangle's first cell in u       */
+    uint64_t rhs_row, rhs_col;       /* where element (0, 0) of the right-hand side is read */
+    uint64_t n_rows, n_cols;
+    double weight[5];                /* n, w, c, e, s -- Cross5's order       */
+    double rhs_coef;
+    double halo;                     /* what a neighbour outside the view of u reads */
+} ststhip_grid_relax_desc;
+int ststhip_grid_relax(int n, const ststhip_grid_relax_desc *relaxations, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

@@ -252,6 +252,16 @@ class GridDotResult(C.Structure):
                 ("sum_bb", C.c_double)]
 
 
+class GridRelaxDesc(C.Structure):
+    """ststhip_grid_relax_desc"""
+
+    _fields_ = [("u", GridView), ("rhs", GridView), ("type", C.c_uint32), ("has_rhs", C.c_uint32),
+                ("first_colour", C.c_uint32), ("n_half_sweeps", C.c_uint32), ("parity", C.c_uint32),
+                ("reserved", C.c_uint32), ("u_row", C.c_uint64), ("u_col", C.c_uint64), ("rhs_row", C.c_uint64),
+                ("rhs_col", C.c_uint64), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64), ("weight", C.c_double * 5),
+                ("rhs_coef", C.c_double), ("halo", C.c_double)]
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -348,6 +358,7 @@ def load():
         "ststhip_grid_resample": [C.c_int, C.POINTER(GridResampleDesc), vp],
         "ststhip_grid_stencil": [C.c_int, C.POINTER(GridStencilDesc), vp],
         "ststhip_grid_dot": [C.c_int, C.POINTER(GridDotDesc), C.POINTER(GridDotResult), vp],
+        "ststhip_grid_relax": [C.c_int, C.POINTER(GridRelaxDesc), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -867,6 +878,30 @@ def grid_dot(pairs, stream=None):
     result = (GridDotResult * max(n, 1))()
     check(load().ststhip_grid_dot(n, table, result, C.c_void_p(int(stream or 0))), "ststhip_grid_dot")
     return result
+
+
+def grid_relax_desc(u, dtype, cross, n_rows, n_cols, u_at=(0, 0), halo=0.0, rhs=None, rhs_coef=1.0, rhs_at=(0, 0),
+                    first_colour=0, half_sweeps=2, parity=0):
+    """A ststhip_grid_relax_desc: `half_sweeps` red-black half-sweeps IN PLACE over the n_rows x n_cols rectangle of view
+    `u` from u_at on.  Half-sweep k updates the cells (r, q) of the view with (r + q + parity) & 1 ==
+    (first_colour + k) & 1: acc = w_n * N, then + w_w * W, + w_c * C, + w_e * E, + w_s * S, then + rhs_coef * rhs where a
+    view `rhs` is given, in `dtype` ('<f4' / '<f8').  `cross`: the five weights (n, w, c, e, s).  `halo` is what a
+    neighbour outside the view reads."""
+    taps = [float(w) for w in cross]
+    if len(taps) != 5:
+        raise ValueError(f"a grid relaxation has five weights (n, w, c, e, s), not {len(taps)}")
+    desc = GridRelaxDesc(u, GridView() if rhs is None else rhs, _algebra_type(dtype), 0 if rhs is None else 1,
+                         int(first_colour), int(half_sweeps), int(parity), 0, int(u_at[0]), int(u_at[1]),
+                         int(rhs_at[0]), int(rhs_at[1]), int(n_rows), int(n_cols))
+    desc.weight[:] = taps
+    desc.rhs_coef, desc.halo = float(rhs_coef), float(halo)
+    return desc
+
+
+def grid_relax(descs, stream=0):
+    """ststhip_grid_relax: 1..8 grid_relax_desc() entries, queued on `stream`; does not synchronise.  The half-sweeps
+    of one entry run in order; the entries in no particular order."""
+    _grid_region_call("ststhip_grid_relax", GridRelaxDesc, descs, stream)
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

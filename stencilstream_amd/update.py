@@ -381,6 +381,51 @@ class Grid:
                                                           float(halo), f, float(rhs_coef), (r0, c0))],
                                   torch_stream.cuda_stream)
 
+    # ---- red-black relaxation in place (ststhip_grid_relax) ----
+    def relax(self, *, cross, halo=0.0, rhs=None, rhs_coef=1.0, field=None, rhs_field=None, rows=None, cols=None,
+              first_colour=0, half_sweeps=2, parity=0):
+        """`half_sweeps` red-black half-sweeps of this[field] IN PLACE over rows[0]:rows[1], cols[0]:cols[1] (None = the
+        whole axis).  Cell (r, q) of the GRID has the colour (r + q + parity) & 1, whatever the rectangle; half-sweep k
+        updates the rectangle's cells of colour (first_colour + k) & 1 with the five taps cross = (n, w, c, e, s) in
+        that order, acc = n * N, then acc = acc + w * W ..., then + rhs_coef * rhs[rhs_field](i, j): every product and
+        every sum is rounded once in the element's dtype, so numpy in the same dtype gives the same bits.  The four
+        neighbours of a cell have the other colour, so nothing is read that the same half-sweep writes.  A neighbour
+        outside the GRID reads `halo`, one outside the rectangle reads the grid.  `rhs` has this grid's extents and may be
+        another member of this grid's cells, never the relaxed element itself.  Gauss-Seidel for
+        (4u - N - W - E - S) / h^2 = f: cross=(.25, .25, 0, .25, .25), rhs=f, rhs_coef=h*h/4; SOR with factor w:
+        cross=(w/4, w/4, 1 - w, w/4, w/4), rhs_coef=w*h*h/4.  Queued; does not wait."""
+        kind, offset = self._float_element(field)
+        taps = np.asarray(cross, dtype=np.float64)
+        if taps.shape != (5,):
+            raise ValueError(f"cross= takes five weights (n, w, c, e, s), not an array of shape {taps.shape}")
+        if not np.all(np.isfinite(taps)):
+            raise ValueError("a weight of the relaxation is not finite")
+        for what, value, allowed in (("first_colour", first_colour, (0, 1)), ("parity", parity, (0, 1)),
+                                     ("half_sweeps", half_sweeps, range(1, 1025))):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value not in allowed:
+                raise ValueError(f"{what} is {value!r}: it takes {allowed[0]} to {allowed[-1]}")
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        its_offset = None
+        if rhs is not None:
+            if not np.isfinite(float(rhs_coef)):
+                raise ValueError("rhs_coef is not finite")
+            if (rhs.height, rhs.width) != (self.height, self.width):
+                raise ValueError("the right-hand side's grid has not the same size as the grid")
+            its_kind, its_offset = rhs._float_element(rhs_field)
+            if its_kind != kind:
+                raise ValueError(f"the right-hand side's element is {its_kind}, the relaxed one {kind}")
+            if rhs.cells.data_ptr() == self.cells.data_ptr() and its_offset == offset:
+                raise ValueError("the right-hand side is the relaxed element itself")
+        elif rhs_field is not None:
+            raise ValueError("rhs_field names a member of a right-hand side that is not given")
+        if r1 > r0 and c1 > c0:
+            with self._on_device() as torch_stream:
+                f = None if rhs is None else rhs._view(its_offset)
+                capi.grid_relax([capi.grid_relax_desc(self._view(offset), kind.str, [float(t) for t in taps], r1 - r0,
+                                                      c1 - c0, (r0, c0), float(halo), f, float(rhs_coef), (r0, c0),
+                                                      int(first_colour), int(half_sweeps), int(parity))],
+                                torch_stream.cuda_stream)
+
     # ---- the inner product of two grids (ststhip_grid_dot) ----
     def dot(self, other=None, field=None, other_field=None, rows=None, cols=None, other_at=None):
         """Dot(n_cells, n_nonfinite, dot, sum_aa, sum_bb): the sums of a * b, a * a and b * b in double over
