@@ -575,6 +575,73 @@ typedef struct {
 } ststhip_grid_relax_desc;
 int ststhip_grid_relax(int n, const ststhip_grid_relax_desc *relaxations, ststhip_stream stream);
 
+/* Grid diffusion: the five-point finite-volume operator whose weights are FACE COEFFICIENTS STORED IN TWO GRIDS (an
+ * extension, as the stencils; additive within ABI 6).  ststhip_grid_stencil and ststhip_grid_relax take constant weights;
+ * this is the variable-coefficient operator A u = sigma u - scale div(k grad u): heterogeneous conduction, an implicit
+ * heat step (sigma + A) u = b, masked domains, Neumann walls.  kx holds the EAST face of every cell, ky its SOUTH face,
+ * so the operator is symmetric by construction; a zero face is an insulated wall, a ring of zero faces cuts a cell out.
+ * Three modes: apply (a residual, CG's A p), one damped Jacobi step (a smoother that needs no colouring) and the diagonal
+ * solve z = r / diag(A) (the Jacobi preconditioner).  Views and element types are the algebra's.
+ *
+ * The result is DEFINED OPERATION BY OPERATION, as the stencil's.  For element (i, j) of the n_rows x n_cols rectangle
+ * let X(a, b) be view X at (X_row + i + a, X_col + j + b):
+ *     c = u(0,0), n = u(-1,0), w = u(0,-1), e = u(0,+1), s = u(+1,0)
+ *     ke = kx(0,0) (this cell's east face), kw = kx(0,-1) (the west neighbour's east face),
+ *     ks = ky(0,0) (this cell's south face), kn = ky(-1,0) (the north neighbour's south face), f = rhs(0,0)
+ * A neighbour outside u's VIEW reads `halo`, one outside the rectangle but inside the view reads the view.  kw outside
+ * kx's view and kn outside ky's view read `k_halo`; every view is judged by its own extents.  Then
+ *     acc = kn*(c-n);  acc = acc + kw*(c-w);  acc = acc + ke*(c-e);  acc = acc + ks*(c-s)
+ *     d = kn + kw;  d = d + ke;  d = d + ks;  d = scale*d;  d = sigma + d
+ *     APPLY:       y = sigma*c;  y = y + scale*acc;  if has_rhs:  y = y + rhs_coef*f
+ *     JACOBI:      t = sigma*c;  t = t + scale*acc;  r = rhs_coef*f;  r = r - t;  y = c + omega*(r/d)
+ *     SOLVE_DIAG:  y = (rhs_coef*f)/d            (u is neither read nor validated)
+ *     dst(0,0) = y
+ * Every product, sum, difference and quotient is rounded once in the element's type and never fused; subnormals are
+ * kept; `/` is the IEEE correctly rounded quotient, and a zero d gives what IEEE gives (+-inf, or NaN for 0/0).
+ * sigma, scale, omega, rhs_coef, halo and k_halo are converted from double once, on the host.  A zero coefficient is
+ * multiplied like every other: 0 * inf is NaN, as in numpy.  JACOBI and SOLVE_DIAG need a right-hand side.
+ *
+ * The conventions are the stencil's: one to eight entries per call, run in NO particular order and not checked against
+ * each other; nothing is clipped; an empty rectangle succeeds on the host, also with null bases and without a device;
+ * n_rows, n_cols and the byte extent of a rectangle's row in every view are below 2^31; bases and strides are
+ * multiples of the element's size; the call is ordered on `stream` and does not synchronise.
+ *
+ * Overlap.  What is read is u's rectangle widened by one cell on every side where that lies inside u's view, kx's
+ * rectangle widened by one cell to the west and ky's by one cell to the north, where their views go on.  The byte span of
+ * each of those may intersect the destination's span in one case only: the view is another member of the destination's
+ * cells by the regions' rule (same stride and pitch, the first elements of the two rectangles d bytes apart with
+ * elem_size <= d and d + elem_size <= stride).  u (or kx, ky) being the destination itself is refused.  rhs may BE the
+ * destination (same first-element address, stride and pitch) or another member of the same cells; every other
+ * intersection is refused.  u, kx, ky and rhs are only read and may overlap each other in any way.
+ *
+ * Arguments are validated before anything touches the device (STSTHIP_ERR_INVALID, ststhip_last_error() starts with
+ * "grid diffusion"): n outside 1..8, a null table, an unknown type or mode, reserved != 0, JACOBI or SOLVE_DIAG without a
+ * right-hand side, stride 0, pitch < width, a null base with a non-empty rectangle, misalignment, extents that describe
+ * more than 2^63 bytes, a rectangle outside its view, a sigma, scale, rhs_coef (with has_rhs) or omega (in JACOBI) that
+ * is not finite (halo and k_halo may be anything), the limits and the overlap rules above.  With has_rhs == 0, rhs,
+ * rhs_row, rhs_col and rhs_coef are ignored; omega is read in JACOBI only; u, u_row and u_col are ignored in SOLVE_DIAG. */
+#define STSTHIP_DIFFUSION_APPLY 0u
+#define STSTHIP_DIFFUSION_JACOBI 1u
+#define STSTHIP_DIFFUSION_SOLVE_DIAG 2u
+typedef struct {
+    ststhip_grid_view dst, u, kx, ky, rhs; /* rhs ignored when has_rhs == 0; u ignored in SOLVE_DIAG */
+    uint32_t type;                   /* STSTHIP_F32 or STSTHIP_F64            */
+    uint32_t mode;                   /* STSTHIP_DIFFUSION_APPLY, _JACOBI or _SOLVE_DIAG */
+    uint32_t has_rhs, reserved;      /* reserved = 0                          */
+    uint64_t dst_row, dst_col;       /* where element (0, 0) of the rectangle lands */
+    uint64_t u_row, u_col;           /* the centre of element (0, 0)          */
+    uint64_t kx_row, kx_col;         /* its east face                         */
+    uint64_t ky_row, ky_col;         /* its south face                        */
+    uint64_t rhs_row, rhs_col;       /* where element (0, 0) of the right-hand side is read */
+    uint64_t n_rows, n_cols;
+    double sigma, scale;             /* A = sigma + scale * (sum of the face fluxes) */
+    double omega;                    /* the damping of a JACOBI step; read there only */
+    double rhs_coef;
+    double halo;                     /* what a neighbour outside the view of u reads */
+    double k_halo;                   /* what kw reads outside kx's view, kn outside ky's */
+} ststhip_grid_diffusion_desc;
+int ststhip_grid_diffusion(int n, const ststhip_grid_diffusion_desc *entries, ststhip_stream stream);
+
 /* ------------------------------------------------------------- layer 1 */
 
 /* Where a buffer sits inside the global grid.  A single-GPU grid has row_origin = 0 and

@@ -262,6 +262,22 @@ class GridRelaxDesc(C.Structure):
                 ("rhs_coef", C.c_double), ("halo", C.c_double)]
 
 
+class GridDiffusionDesc(C.Structure):
+    """ststhip_grid_diffusion_desc"""
+
+    _fields_ = [("dst", GridView), ("u", GridView), ("kx", GridView), ("ky", GridView), ("rhs", GridView),
+                ("type", C.c_uint32), ("mode", C.c_uint32), ("has_rhs", C.c_uint32), ("reserved", C.c_uint32),
+                ("dst_row", C.c_uint64), ("dst_col", C.c_uint64), ("u_row", C.c_uint64), ("u_col", C.c_uint64),
+                ("kx_row", C.c_uint64), ("kx_col", C.c_uint64), ("ky_row", C.c_uint64), ("ky_col", C.c_uint64),
+                ("rhs_row", C.c_uint64), ("rhs_col", C.c_uint64), ("n_rows", C.c_uint64), ("n_cols", C.c_uint64),
+                ("sigma", C.c_double), ("scale", C.c_double), ("omega", C.c_double), ("rhs_coef", C.c_double),
+                ("halo", C.c_double), ("k_halo", C.c_double)]
+
+
+# STSTHIP_DIFFUSION_APPLY, STSTHIP_DIFFUSION_JACOBI, STSTHIP_DIFFUSION_SOLVE_DIAG
+DIFFUSION_APPLY, DIFFUSION_JACOBI, DIFFUSION_SOLVE_DIAG = 0, 1, 2
+
+
 class NoParams(C.Structure):
     _fields_ = [("unused", C.c_int)]
 
@@ -359,6 +375,7 @@ def load():
         "ststhip_grid_stencil": [C.c_int, C.POINTER(GridStencilDesc), vp],
         "ststhip_grid_dot": [C.c_int, C.POINTER(GridDotDesc), C.POINTER(GridDotResult), vp],
         "ststhip_grid_relax": [C.c_int, C.POINTER(GridRelaxDesc), vp],
+        "ststhip_grid_diffusion": [C.c_int, C.POINTER(GridDiffusionDesc), vp],
         "ststhip_app_count": [],
         "ststhip_app_info_at": [C.c_int, C.POINTER(AppInfo)],
         "ststhip_app_find": [C.c_char_p, C.POINTER(AppInfo)],
@@ -902,6 +919,30 @@ def grid_relax(descs, stream=0):
     """ststhip_grid_relax: 1..8 grid_relax_desc() entries, queued on `stream`; does not synchronise.  The half-sweeps
     of one entry run in order; the entries in no particular order."""
     _grid_region_call("ststhip_grid_relax", GridRelaxDesc, descs, stream)
+
+
+def grid_diffusion_desc(dst, u, kx, ky, dtype, mode, n_rows, n_cols, dst_at=(0, 0), u_at=(0, 0), kx_at=(0, 0),
+                        ky_at=(0, 0), sigma=0.0, scale=1.0, omega=1.0, halo=0.0, k_halo=0.0, rhs=None, rhs_coef=1.0,
+                        rhs_at=(0, 0)):
+    """A ststhip_grid_diffusion_desc: over the n_rows x n_cols rectangle the five-point operator whose weights are the
+    face coefficients of views `kx` (east faces) and `ky` (south faces), in `dtype` ('<f4' / '<f8'):
+    acc = kn*(c-n), + kw*(c-w), + ke*(c-e), + ks*(c-s); d = sigma + scale*(((kn+kw)+ke)+ks).  `mode` DIFFUSION_APPLY:
+    sigma*c + scale*acc (+ rhs_coef*rhs); DIFFUSION_JACOBI: c + omega*((rhs_coef*rhs - (sigma*c + scale*acc))/d);
+    DIFFUSION_SOLVE_DIAG: (rhs_coef*rhs)/d, where `u` may be None.  `halo` is what a neighbour outside the view `u`
+    reads, `k_halo` what kw and kn read outside the views `kx` and `ky`."""
+    desc = GridDiffusionDesc(dst, GridView() if u is None else u, kx, ky, GridView() if rhs is None else rhs,
+                             _algebra_type(dtype), int(mode), 0 if rhs is None else 1, 0, int(dst_at[0]),
+                             int(dst_at[1]), int(u_at[0]), int(u_at[1]), int(kx_at[0]), int(kx_at[1]), int(ky_at[0]),
+                             int(ky_at[1]), int(rhs_at[0]), int(rhs_at[1]), int(n_rows), int(n_cols))
+    desc.sigma, desc.scale, desc.omega = float(sigma), float(scale), float(omega)
+    desc.rhs_coef, desc.halo, desc.k_halo = float(rhs_coef), float(halo), float(k_halo)
+    return desc
+
+
+def grid_diffusion(entries, stream=0):
+    """ststhip_grid_diffusion: 1..8 grid_diffusion_desc() entries, queued on `stream`; does not synchronise.  The
+    entries run in no particular order."""
+    _grid_region_call("ststhip_grid_diffusion", GridDiffusionDesc, entries, stream)
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

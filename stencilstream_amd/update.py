@@ -426,6 +426,66 @@ class Grid:
                                                       int(first_colour), int(half_sweeps), int(parity))],
                                 torch_stream.cuda_stream)
 
+    # ---- the five-point operator with face coefficients in two grids (ststhip_grid_diffusion) ----
+    def diffusion(self, src, kx, ky, *, mode="apply", sigma=0.0, scale=1.0, omega=1.0, halo=0.0, k_halo=0.0, rhs=None,
+                  rhs_coef=1.0, field=None, src_field=None, kx_field=None, ky_field=None, rhs_field=None, rows=None,
+                  cols=None):
+        """The finite-volume operator A u = sigma u + scale * sum of k (u_c - u_neighbour) over the four faces of a
+        cell, with the face coefficients in two grids: kx[kx_field](i, j) is the EAST face of cell (i, j),
+        ky[ky_field](i, j) its SOUTH face; the west face is kx(i, j-1), the north face ky(i-1, j).  Over rows[0]:rows[1],
+        cols[0]:cols[1] (None = the whole axis; one rectangle applies to all grids, which have this grid's extents, any
+        cell type and elements of this element's dtype):
+            acc = kn*(c-n); acc = acc + kw*(c-w); acc = acc + ke*(c-e); acc = acc + ks*(c-s)
+            d = sigma + scale*(((kn + kw) + ke) + ks)
+            mode="apply":       this[field] = sigma*c + scale*acc (+ rhs_coef * rhs)
+            mode="jacobi":      this[field] = c + omega * ((rhs_coef*rhs - (sigma*c + scale*acc)) / d)
+            mode="solve_diag":  this[field] = (rhs_coef * rhs) / d          (src may be None; a src and src_field
+                                                                             that are given are ignored, unchecked)
+        Every operation is rounded once in that dtype and `/` is the IEEE quotient, so numpy in the same dtype gives
+        the same bits.  A neighbour of `src` outside the GRID reads `halo`; the west face of column 0 and the north face
+        of row 0 read `k_halo`.  "jacobi" and "solve_diag" need `rhs`.  `src`, `kx` and `ky` may be other members of this
+        grid's cells but not the destination itself; `rhs` may be either.  Queued; does not wait."""
+        kind, offset = self._float_element(field)
+        modes = {"apply": capi.DIFFUSION_APPLY, "jacobi": capi.DIFFUSION_JACOBI, "solve_diag": capi.DIFFUSION_SOLVE_DIAG}
+        if mode not in modes:
+            raise ValueError(f"mode is {mode!r}: it takes 'apply', 'jacobi' or 'solve_diag'")
+        if mode != "apply" and rhs is None:
+            raise ValueError(f"mode {mode!r} needs a right-hand side")
+        if src is None and mode != "solve_diag":
+            raise ValueError(f"mode {mode!r} needs a source; only 'solve_diag' reads none")
+        if src is None and src_field is not None:
+            raise ValueError("src_field names a member of a source that is not given")
+        for what, value, read in (("sigma", sigma, True), ("scale", scale, True), ("omega", omega, mode == "jacobi"),
+                                  ("rhs_coef", rhs_coef, rhs is not None)):
+            if read and not np.isfinite(float(value)):
+                raise ValueError(f"{what} is not finite")
+        (r0, r1), (c0, c1) = self._axis(rows, self.height, "rows"), self._axis(cols, self.width, "columns")
+        others = [("the east faces", kx, kx_field), ("the south faces", ky, ky_field)]
+        if mode != "solve_diag":
+            others.append(("the source", src, src_field))
+        if rhs is not None:
+            others.append(("the right-hand side", rhs, rhs_field))
+        elif rhs_field is not None:
+            raise ValueError("rhs_field names a member of a right-hand side that is not given")
+        views = {}
+        for what, grid, its_field in others:
+            if (grid.height, grid.width) != (self.height, self.width):
+                raise ValueError(f"{what}'s grid has not the same size as the grid")
+            its_kind, its_offset = grid._float_element(its_field)
+            if its_kind != kind:
+                raise ValueError(f"{what}'s element is {its_kind}, the destination's {kind}")
+            if what != "the right-hand side" and grid.cells.data_ptr() == self.cells.data_ptr() and its_offset == offset:
+                raise ValueError(f"{what} is the destination itself: an operator in place is a race")
+            views[what] = grid._view(its_offset)
+        if r1 > r0 and c1 > c0:
+            with self._on_device() as torch_stream:
+                at = (r0, c0)
+                capi.grid_diffusion([capi.grid_diffusion_desc(
+                    self._view(offset), views.get("the source"), views["the east faces"], views["the south faces"],
+                    kind.str, modes[mode], r1 - r0, c1 - c0, at, at, at, at, float(sigma), float(scale), float(omega),
+                    float(halo), float(k_halo), views.get("the right-hand side"), float(rhs_coef), at)],
+                    torch_stream.cuda_stream)
+
     # ---- the inner product of two grids (ststhip_grid_dot) ----
     def dot(self, other=None, field=None, other_field=None, rows=None, cols=None, other_at=None):
         """Dot(n_cells, n_nonfinite, dot, sum_aa, sum_bb): the sums of a * b, a * a and b * b in double over
